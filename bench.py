@@ -9,7 +9,15 @@ contract. `--gpus N` without torchrun's environment relaunches this script under
 `torch.distributed.run` with N ranks (before anything touches a GPU), so
 `python bench.py --gpus 8` and the driver's torchrun line run the same code.
 
-Besides the headline number the JSON line carries:
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline figure needs:
+it uploads the squares, runs W untimed and K timed steps and prints the JSON line with
+the headline fields (metric, value, unit, ms_per_step, dtype, config, ...).
+`--dump-outputs DIR` also writes what the last timed step left in its batch's buffers
+(dump_outputs below). Every other measurement runs only with `--full`; the `--no-*`
+options then take single parts out of it. The other `--mode`s are measurements of their
+own and do not change with `--full`, except that distcheck carries its riders only then.
+
+With `--full` the JSON line also carries:
   roofline      RS extension (both passes) vs HBM: algorithmic 2048 k^2 bytes per
                 square / measured average duration (HIP events on the launch stream)
   roofline_nmt  NMT+DAH phase: SHA-256 compressions (60 k^2 + 4k - 2 per square)
@@ -89,6 +97,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="batch mode: besides the headline also the same-run probe, the phase rooflines, power, "
+                         "the k=512 line, the riders, host_io and the CPU baseline (each --no-* takes its part "
+                         "out again); distcheck mode: the riders' CPU stand-ins")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="batch mode: after the timed steps write the last step's outputs (EDS sample, row and "
+                         "column roots, DAHs, statuses of rank 0's batch) as DIR/<name>.npy")
     ap.add_argument("--k", type=int, default=128, help="original square width")
     ap.add_argument("--batch", type=int, default=256, help="squares per step per GPU")
     ap.add_argument("--distinct", type=int, default=4, help="distinct synthetic squares per GPU")
@@ -188,7 +203,7 @@ def run_distcheck(a):
     # the riders' assembly with CPU stand-ins: the k64 split and, for the row-sharded
     # square, the same all_to_all_single shape (k = 64 here) over gloo, timed the same way
     riders = {}
-    if not a.no_riders:
+    if a.full and not a.no_riders:
         riders["k64"] = _k64_fields(world, elapsed, a.steps)
         k = 64
         per_peer = 2 * k * k * 512 // (world * world)
@@ -1008,11 +1023,39 @@ def _rider(result, name, fn):
     torch.cuda.empty_cache()
 
 
+DUMP_ELEMS = 16_000_000  # float32 elements --dump-outputs may write in all (64 MB)
+DUMP_SEED = 408
+# (buffer of the batch, its share of DUMP_ELEMS in 64ths): at the default shapes only the
+# EDS (8 GiB) is sampled
+DUMP_ARRAYS = (("eds", 12), ("row_roots", 24), ("col_roots", 24), ("dah", 1), ("status", 1))
+
+
+def dump_outputs(dirname, sb):
+    """Write what a caller of cel_dev_extend_batch receives from the batch `sb`, as
+    <dirname>/<name>.npy in float32 (bytes and statuses are exact there): eds, row_roots,
+    col_roots, dah, status. A buffer larger than its share of DUMP_ELEMS is sampled in
+    units of its last axis (whole 512-byte shares, whole 90-byte roots): a sorted draw
+    without replacement from default_rng(DUMP_SEED), so the same arguments give the same
+    units, and the file is then [units][last axis]."""
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, share in DUMP_ARRAYS:
+        t = getattr(sb, name)
+        cap = DUMP_ELEMS * share // 64
+        if t.numel() > cap:
+            unit = t.shape[-1] if t.dim() > 1 else 1
+            rows = t.reshape(-1, unit)
+            pick = np.sort(rng.choice(rows.shape[0], size=max(1, cap // unit), replace=False, shuffle=False))
+            t = rows.index_select(0, torch.from_numpy(pick).to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def _measure_batch(ctx, local, rank, k, B, steps, warmup, n_distinct, layout, phase_reps, barrier, dist, dev,
-                   inflight=1):
+                   inflight=1, phases=True, dump_dir=None):
     """Time `steps` batch steps of B k x k squares resident in HBM (barrier + synchronize
-    on both sides, max over ranks), then the RS and NMT phases alone with HIP events on
-    the batch's launch stream. inflight > 1: that many batches (own buffers and stream
+    on both sides, max over ranks), then (phases) the RS and NMT phases alone with HIP events on
+    the batch's launch stream. dump_dir: dump_outputs of the batch the last timed step ran on,
+    before anything else touches it. inflight > 1: that many batches (own buffers and stream
     each) take the steps in turn, each step as one chunk on its batch's stream
     (CEL_FLAG_CALLER_STREAM), so one step's latency-bound tree tops and DAH run beside the
     next step's bulk (independent blocks replayed back to back); every step still extends
@@ -1045,8 +1088,12 @@ def _measure_batch(ctx, local, rank, k, B, steps, warmup, n_distinct, layout, ph
     for sb in sbs:
         status = sb.status.cpu().numpy()
         assert (status == 0).all(), f"device reported status {status}"
+    if dump_dir is not None:
+        dump_outputs(dump_dir, sbs[(steps - 1) % len(sbs)] if steps > 0 else sbs[0])
     sb = sbs[0]
     del sbs
+    if not phases:
+        return {"sb": sb, "distinct": distinct, "elapsed": elapsed, "t_ext": None, "t_com": None}
 
     stream = sb.hip_stream  # the stream every launch of `sb` goes to
 
@@ -1202,6 +1249,16 @@ def measure_host_io(ctx, k, n=16, reps=5):
     return out
 
 
+def _emit(result, rank, dist):
+    """The end of a batch-mode run: rank 0 prints the JSON line."""
+    if REHEARSE:
+        result["config"]["rehearsal"] = "all ranks on cuda:0, gloo with host staging: not a multi-GPU measurement"
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
 def main():
     global REHEARSE
     a = parse()
@@ -1233,22 +1290,20 @@ def main():
             dist.barrier()
 
     probe = None
-    try:
-        probe = measure_probe(ctx)
-    except Exception as e:  # noqa: BLE001  (the line keeps its fixed-constant fractions)
-        print(f"bench: probe failed: {e!r}", file=sys.stderr, flush=True)
+    if a.full:
+        try:
+            probe = measure_probe(ctx)
+        except Exception as e:  # noqa: BLE001  (the line keeps its fixed-constant fractions)
+            print(f"bench: probe failed: {e!r}", file=sys.stderr, flush=True)
     m = _measure_batch(ctx, local, rank, a.k, a.batch, a.steps, a.warmup, a.distinct, a.input,
-                       a.phase_reps, barrier, dist, dev, a.inflight)
+                       a.phase_reps, barrier, dist, dev, a.inflight, phases=a.full,
+                       dump_dir=a.dump_outputs if rank == 0 else None)
     k, B, elapsed, t_ext, t_com = a.k, a.batch, m["elapsed"], m["t_ext"], m["t_com"]
     sb, distinct = m["sb"], m["distinct"]
     del m
     squares = world * B * a.steps
     value = squares / elapsed
     ods_bytes = 512 * k * k
-    rs_bytes = 2048 * k * k * B  # read ODS + write Q1..Q3, per launch pair
-    rs_gbs = rs_bytes / t_ext / 1e9
-    compressions = (60 * k * k + 4 * k - 2) * B
-    nmt_rate = compressions / t_com
 
     result = {
         "metric": "EDS+DAH squares/sec (k=%d)" % k,
@@ -1275,6 +1330,14 @@ def main():
                              else "contiguous ODS buffer"),
             "batches_in_flight": a.inflight,
         },
+    }
+    if not a.full:
+        return _emit(result, rank, dist)
+    rs_bytes = 2048 * k * k * B  # read ODS + write Q1..Q3, per launch pair
+    rs_gbs = rs_bytes / t_ext / 1e9
+    compressions = (60 * k * k + 4 * k - 2) * B
+    nmt_rate = compressions / t_com
+    result.update({
         "roofline": {
             "bound": "hbm",
             "kernel": ("rs_extend (k_rs_axis_gf8 rows + cols launches)" if 32 <= k <= 128
@@ -1303,7 +1366,7 @@ def main():
                                 "issue model), 1024 SIMDs, 2.4 GHz",
             "avg_launch_us": t_com * 1e6,
         },
-    }
+    })
     if probe:
         # same-run denominators (cel_probe_*, before the timed region, this rank's device)
         result["probe"] = {**probe, "basis": "cel_probe_sha256 (NMT compression chained in registers, 16 WG/CU; "
@@ -1391,12 +1454,7 @@ def main():
             return base
 
         _rider(result, "cpu_baseline", cpu)
-    if REHEARSE:
-        result["config"]["rehearsal"] = "all ranks on cuda:0, gloo with host staging: not a multi-GPU measurement"
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    _emit(result, rank, dist)
 
 
 if __name__ == "__main__":

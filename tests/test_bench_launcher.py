@@ -40,7 +40,7 @@ def test_riders_in_multi_rank_line():
     """One N-rank command carries configs 4 and 3 as riders (k64: 1024/N squares per rank;
     rowshard512: the row-sharded square's all_to_all_single, timed alone, beside SURVEY
     §8e's one-link estimate), with n_gpus = N. Here over gloo with CPU stand-in steps."""
-    out = _run(["--gpus", "4", "--mode", "distcheck", "--steps", "2", "--warmup", "1"])
+    out = _run(["--gpus", "4", "--mode", "distcheck", "--steps", "2", "--warmup", "1", "--full"])
     assert len(out) == 1, out
     r = out[0]
     assert r["n_gpus"] == 4
@@ -53,6 +53,41 @@ def test_riders_in_multi_rank_line():
     # other ranks wait on the gloo idle group; both reach the line with all N devices
     for name in ("rowshard512_lib", "k64_lib"):
         assert r[name]["devices"] == [0, 1, 2, 3] and r[name]["value"] > 0
+
+
+def test_plain_line_carries_no_riders():
+    """Without --full the line holds the headline fields only."""
+    r = _run(["--mode", "distcheck", "--steps", "2", "--warmup", "0"])[0]
+    assert r["steps"] == 2 and r["ms_per_step"] > 0
+    assert not {"k64", "rowshard512", "rowshard512_lib", "k64_lib"} & set(r)
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: every buffer of the batch as float32 .npy; one over its share of
+    DUMP_ELEMS is sampled in whole units of its last axis, the same units on every call."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    u8 = lambda *s: torch.randint(0, 256, s, dtype=torch.uint8, generator=g)  # noqa: E731
+    sb = types.SimpleNamespace(eds=u8(3, 8, 8, 512), row_roots=u8(3, 8, 90), col_roots=u8(3, 8, 90),
+                               dah=u8(3, 32), status=torch.zeros(3, dtype=torch.int32))
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 64 * 512)  # eds: 12/64 of it = 12 shares of its 192
+    bench.dump_outputs(str(tmp_path / "a"), sb)
+    bench.dump_outputs(str(tmp_path / "b"), sb)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n, _ in bench.DUMP_ARRAYS}
+    assert all(v.dtype == np.float32 for v in got.values())
+    for n in ("row_roots", "col_roots", "dah", "status"):
+        assert np.array_equal(got[n], getattr(sb, n).numpy())
+    shares = sb.eds.reshape(-1, 512).numpy()
+    assert got["eds"].shape == (12, 512)
+    rows = [int(np.flatnonzero((shares == s).all(axis=1))[0]) for s in got["eds"]]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(got["eds"], np.load(tmp_path / "b" / "eds.npy"))
+    assert sum(v.nbytes for v in got.values()) <= 4 * 64 * 512
 
 
 def test_step_ceiling_fields():

@@ -21,7 +21,7 @@ def test_two_rank_rehearsal():
         env.pop(v, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "2", "--warmup",
            "1", "--batch", "16", "--k512-batch", "2", "--k512-steps", "2", "--rider-steps", "2", "--phase-reps", "2",
-           "--no-host-io", "--no-cpu"]
+           "--no-host-io", "--no-cpu", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

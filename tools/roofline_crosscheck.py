@@ -1,4 +1,4 @@
-"""Cross-check of bench.py's roofline numbers against a rocprofv3 kernel trace of the same
+"""Cross-check of `bench.py --full`'s roofline numbers against a rocprofv3 kernel trace of the same
 command (VERDICT r3 ask 4).
 
 The bench times `extend_only` (the RS launch pair) and `commit_only` (the NMT + DAH launches)
@@ -77,7 +77,7 @@ def main():
         d[(r["Kernel_Name"], int(r["Grid_Size_X"]))].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     out = []
     P = out.append
-    P(f"# roofline cross-check: rocprofv3 --kernel-trace of `python3 bench.py` vs its JSON line")
+    P(f"# roofline cross-check: rocprofv3 --kernel-trace of `python3 bench.py --full` vs its JSON line")
     P(f"# trace: {tdir}; line: {bjson}; k={k}, B={B}; launch stream {stream[0]} (queue {stream[1]}),")
     P(f"# the stream of the phase timing's full-batch RS launches, from the first of them")
     P(f"# (with batches in flight: from the other batches' last launch) to the next")
