@@ -75,6 +75,11 @@ void cel_ctx_destroy(cel_ctx* ctx) {
     for (int i = 0; i < 6; i++)
       if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->hstage) (void)hipHostFree(ctx->hstage);
+    if (ctx->ev_plan) {
+      (void)hipEventSynchronize(ctx->ev_plan);  // a caller stream may still read plan_stage
+      (void)hipEventDestroy(ctx->ev_plan);
+    }
+    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
     free_tables(&ctx->tables);
     for (int i = 0; i < cel_ctx::kPipe; i++)
       if (ctx->sub[i]) (void)hipStreamDestroy(ctx->sub[i]);

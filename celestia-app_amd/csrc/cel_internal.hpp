@@ -212,6 +212,17 @@ hipError_t launch_commitment(const uint8_t* d_cells, uint32_t k, uint32_t r0, ui
                              uint32_t* d_nodes, uint8_t* d_items, void* d_merkle_work, uint8_t* d_out,
                              hipStream_t s);
 
+// Blob share commitments from blob bytes (blob_commit.hip; plan and layout: blob_plan.hpp).
+// d_work: blob_commit_workspace_size bytes whose head already holds the plan's tables (the
+// records, then, 256-aligned, the slot table); d_out: 32 bytes per blob. d_shares (optional,
+// plan.slots * 512 bytes): the A/B partner of the leaf stage, shares expanded into it first.
+namespace blob {
+struct Plan;
+}
+size_t blob_commit_workspace_size(uint64_t slots, uint64_t roots, uint32_t nblobs);
+hipError_t launch_blob_commit(const uint8_t* d_data, const blob::Plan& plan, void* d_work, uint8_t* d_out,
+                              hipStream_t s, uint32_t* d_shares = nullptr);
+
 // Erasure decode of `naxes` axes of 2n shards each, gathered into a dense
 // [naxes][2n][len] buffer with a [naxes][2n] present mask. In place.
 // GF(2^16) erasure decode over n = 512, 1024 or 2048 points (rs_decode_gf16.hip).
@@ -262,6 +273,13 @@ struct cel_ctx {
   // Grow-only page-locked host staging (the repair's axis lists).
   void* hstage = nullptr;
   size_t hstage_size = 0;
+  // Page-locked plan tables of the blob commitment calls (api_commit.cpp). The asynchronous
+  // entry returns while their upload may still be queued, so they have a buffer of their
+  // own and the next call waits for ev_plan (recorded after the upload) before refilling it.
+  void* plan_stage = nullptr;
+  size_t plan_stage_size = 0;
+  hipEvent_t ev_plan = nullptr;
+  bool plan_pending = false;
   // Schedule fuzzing of the repair's two streams (cel_debug_schedule_fuzz; tests only):
   // before each enqueue point, an idle kernel of 0..fuzz_max_us microseconds.
   uint64_t fuzz_state = 0;

@@ -11,27 +11,16 @@
 #include <vector>
 
 #include "../../include/celestia_eds.h"
+#include "blob_plan.hpp"
 
 namespace cel {
 namespace incl {
 namespace {
 
-uint32_t pow2ceil(uint64_t n) {
-  uint32_t r = 1;
-  while (r < n) r <<= 1;
-  return r;
-}
-uint32_t log2u(uint32_t n) {
-  uint32_t l = 0;
-  while ((1u << l) < n) l++;
-  return l;
-}
-// go-square inclusion.SubTreeWidth: min(RoundUpPow2(ceil(n / threshold)), BlobMinSquareSize(n))
-uint32_t subtree_width(uint32_t shares, uint32_t threshold) {
-  const uint32_t s = pow2ceil((shares + threshold - 1) / threshold);
-  const uint32_t m = pow2ceil((uint64_t)std::ceil(std::sqrt((double)shares)));
-  return s < m ? s : m;
-}
+// go-square inclusion.SubTreeWidth and its helpers: blob_plan.hpp
+using blob::log2u;
+using blob::pow2ceil;
+using blob::subtree_width;
 
 struct Coord {
   uint32_t depth, position;

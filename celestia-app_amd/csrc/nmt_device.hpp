@@ -1,0 +1,265 @@
+// Device building blocks of the NMT and RFC-6962 hashing shared by nmt_kernels.hip (the EDS
+// commit) and blob_commit.hip (blob share commitments): 96-byte node records, the leaf hash
+// of a 512-byte share, HashNode with IgnoreMaxNamespace, and the RFC-6962 leaf / inner
+// hashes. One message per lane.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "cel_internal.hpp"
+#include "sha256_device.hpp"
+
+namespace cel {
+
+__device__ __forceinline__ void load_node(const uint32_t* p, uint32_t (&n)[kNodeWords]) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const uint4 v = q[i];
+    n[4 * i] = v.x; n[4 * i + 1] = v.y; n[4 * i + 2] = v.z; n[4 * i + 3] = v.w;
+  }
+}
+
+__device__ __forceinline__ void store_node(uint32_t* p, const uint32_t (&n)[kNodeWords]) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+#pragma unroll
+  for (int i = 0; i < 6; i++) q[i] = make_uint4(n[4 * i], n[4 * i + 1], n[4 * i + 2], n[4 * i + 3]);
+}
+
+// Node dwords 14..23 from the 8 big-endian digest words (digest = node bytes 58..89).
+// nd14 keeps its low 16 bits (the last two max-namespace bytes).
+__device__ __forceinline__ void put_digest(uint32_t (&nd)[kNodeWords], const uint32_t (&st)[8]) {
+  uint32_t sw[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) sw[i] = bswap32(st[i]);
+  nd[14] = (nd[14] & 0xFFFFu) | (sw[0] << 16);
+#pragma unroll
+  for (int i = 15; i <= 21; i++) nd[i] = __builtin_amdgcn_alignbyte(sw[i - 14], sw[i - 15], 2);
+  nd[22] = sw[7] >> 16;
+  nd[23] = 0;
+}
+
+// --------------------------------------------------------------------- leaves
+
+// Leaf message: 0x00 || ns(29) || share(512) = 542 B -> 9 blocks.
+// sh = the share's little-endian dwords; ns = share[0:29] for Q0 cells, 0xFF*29 else.
+// Message word at byte p >= 32 is share bytes q..q+3 with q = p - 30 (q = 2 mod 4):
+// bytes 2,3 of dword (q-2)/4 and bytes 0,1 of the next -> one v_perm_b32 (and the
+// byte swap to big-endian comes for free in the same select).
+// Parity cells: message bytes 0..27 are 0x00 || 0xFF*27 (ns = 0xFF*29 continues into w7).
+constexpr uint32_t kLeafParPrefix[7] = {0x00FFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu,
+                                        0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+constexpr ShaMid kLeafParMid = sha_midstate(kLeafParPrefix, 7);
+
+// PF (prefetch): the next block's words are loaded while the current block is compressed.
+// At one or two waves per SIMD (a single square's commit, a rank's slab) nothing else
+// covers a block's load latency, which the plain form exposes nine times per leaf; at
+// batch occupancy other waves cover it and the 17 extra VGPRs cost 1.5-3 %
+// (profiles/r2_nmt_leaf_prefetch_ab.txt), so the batch keeps PF = false.
+template <bool PF>
+__device__ __forceinline__ void leaf_hash(uint32_t (&st)[8], const uint32_t* __restrict__ sh, bool q0) {
+  sha256_init(st);
+  uint32_t w[16];
+  uint32_t nx[17];  // PF: the next block's share dwords
+  auto load17 = [&](int b) {  // share bytes [64b-30, 64b+34) for block b = 1..7
+    const uint32_t* base = sh + 16 * b - 8;
+    const uint4* p4 = reinterpret_cast<const uint4*>(base);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint4 v = p4[i];
+      nx[4 * i] = v.x; nx[4 * i + 1] = v.y; nx[4 * i + 2] = v.z; nx[4 * i + 3] = v.w;
+    }
+    nx[16] = base[16];
+  };
+  {  // block 0: 0x00 || ns || share[0:34]
+    uint32_t s[9];
+    const uint4* p4 = reinterpret_cast<const uint4*>(sh);
+    const uint4 v0 = p4[0], v1 = p4[1];
+    s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w; s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+    s[8] = sh[8];
+    if (PF) load17(1);
+#pragma unroll
+    for (int i = 8; i < 16; i++) w[i] = perm(s[i - 8], s[i - 7], 0x06070001u);
+    if (__all(!q0)) {  // wave-uniform parity cells: rounds 0..6 are one constant
+#pragma unroll
+      for (int i = 0; i < 7; i++) w[i] = kLeafParPrefix[i];
+      w[7] = 0xFFFF0000u | perm(0u, s[0], 0x0C0C0001u);
+      sha256_compress_from<7>(st, mid_regs(kLeafParMid), w);
+    } else {
+      if (q0) {
+        w[0] = perm(0u, s[0], 0x0C000102u);
+#pragma unroll
+        for (int i = 1; i < 7; i++) w[i] = perm(s[i - 1], s[i], 0x07000102u);
+        w[7] = perm(s[6], s[7], 0x07000C0Cu) | perm(0u, s[0], 0x0C0C0001u);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 7; i++) w[i] = kLeafParPrefix[i];
+        w[7] = 0xFFFF0000u | perm(0u, s[0], 0x0C0C0001u);
+      }
+      sha256_compress(st, w);
+    }
+  }
+#pragma unroll 1
+  for (int b = 1; b < 8; b++) {  // blocks 1..7: share bytes [64b-30, 64b+34)
+    if (!PF) load17(b);
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = perm(nx[i], nx[i + 1], 0x06070001u);
+    if (PF) {
+      if (b < 7) {
+        load17(b + 1);
+      } else {  // the last block's 8 dwords
+        const uint4* p4 = reinterpret_cast<const uint4*>(sh + 120);
+        const uint4 v0 = p4[0], v1 = p4[1];
+        nx[0] = v0.x; nx[1] = v0.y; nx[2] = v0.z; nx[3] = v0.w; nx[4] = v1.x; nx[5] = v1.y; nx[6] = v1.z; nx[7] = v1.w;
+      }
+    }
+    sha256_compress(st, w);
+  }
+  {  // block 8: share[482:512] || 0x80 || 0... || len
+    if (!PF) {
+      const uint4* p4 = reinterpret_cast<const uint4*>(sh + 120);
+      const uint4 v0 = p4[0], v1 = p4[1];
+      nx[0] = v0.x; nx[1] = v0.y; nx[2] = v0.z; nx[3] = v0.w; nx[4] = v1.x; nx[5] = v1.y; nx[6] = v1.z; nx[7] = v1.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) w[i] = perm(nx[i], nx[i + 1], 0x06070001u);
+    w[7] = perm(nx[7], 0x80u, 0x0607000Cu);
+#pragma unroll
+    for (int i = 8; i < 15; i++) w[i] = 0u;
+    w[15] = 542u * 8u;
+    sha256_compress(st, w);
+  }
+}
+
+// Leaf node of one EDS cell: ns || ns || SHA256(0x00 || ns || share), ns = share[0:29]
+// for Q0 cells and 0xFF*29 (parity namespace) otherwise.
+template <bool PF>
+__device__ __forceinline__ void make_leaf_node(const uint32_t* __restrict__ sh, bool q0, uint32_t (&nd)[kNodeWords]) {
+  uint32_t st[8];
+  leaf_hash<PF>(st, sh, q0);
+  if (q0) {
+    const uint4* p4 = reinterpret_cast<const uint4*>(sh);
+    uint32_t s[8];
+    const uint4 v0 = p4[0], v1 = p4[1];
+    s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w; s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+#pragma unroll
+    for (int i = 0; i < 7; i++) nd[i] = s[i];
+    nd[7] = (s[7] & 0xFFu) | (s[0] << 8);
+#pragma unroll
+    for (int i = 0; i < 6; i++) nd[8 + i] = __builtin_amdgcn_alignbyte(s[i + 1], s[i], 3);
+    nd[14] = (s[6] >> 24) | ((s[7] & 0xFFu) << 8);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 14; i++) nd[i] = 0xFFFFFFFFu;
+    nd[14] = 0xFFFFu;
+  }
+  put_digest(nd, st);
+}
+
+// ---------------------------------------------------------------- inner nodes
+
+// HashNode(L, R): message 0x01 || L(90) || R(90) = 181 B -> 3 blocks.
+// minNs = L.min; maxNs = (R.min == 0xFF*29) ? L.max : R.max  (IgnoreMaxNamespace).
+// Parity left child (min = max = 0xFF*29, nodes of Q1-Q3): message bytes 0..55 are
+// 0x01 || 0xFF*55 for every such node, so rounds 0..13 of block 0 are one constant.
+constexpr uint32_t kNodeParPrefix[14] = {0x01FFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu,
+                                         0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu,
+                                         0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+constexpr ShaMid kNodeParMid = sha_midstate(kNodeParPrefix, 14);
+
+__device__ __forceinline__ uint32_t node_word(const uint32_t (&L)[kNodeWords], const uint32_t (&R)[kNodeWords], int q) {
+  if (q == 0) return perm(1u, L[0], 0x04000102u);
+  if (q <= 21) return perm(L[q - 1], L[q], 0x07000102u);
+  if (q == 22) return perm(L[21], L[22], 0x0700010Cu) | (R[0] & 0xFFu);
+  if (q <= 44) return perm(R[q - 23], R[q - 22], 0x05060700u);
+  if (q == 45) return perm(R[22], 0x80u, 0x05000C0Cu);
+  if (q == 47) return 181u * 8u;
+  return 0u;
+}
+
+__device__ __forceinline__ void hash_node(const uint32_t (&L)[kNodeWords], const uint32_t (&R)[kNodeWords],
+                                          uint32_t (&out)[kNodeWords]) {
+  uint32_t st[8];
+  sha256_init(st);
+  bool lpar = (L[14] & 0xFFFFu) == 0xFFFFu;
+#pragma unroll
+  for (int i = 0; i < 14; i++) lpar = lpar && (L[i] == 0xFFFFFFFFu);
+  {
+    uint32_t w[16];
+    if (__all(lpar)) {  // wave-uniform: the whole wave starts block 0 at round 14
+#pragma unroll
+      for (int wi = 0; wi < 14; wi++) w[wi] = kNodeParPrefix[wi];
+      w[14] = node_word(L, R, 14);
+      w[15] = node_word(L, R, 15);
+      sha256_compress_from<14>(st, mid_regs(kNodeParMid), w);
+    } else {
+#pragma unroll
+      for (int wi = 0; wi < 16; wi++) w[wi] = node_word(L, R, wi);
+      sha256_compress(st, w);
+    }
+  }
+#pragma unroll
+  for (int b = 1; b < 3; b++) {
+    uint32_t w[16];
+#pragma unroll
+    for (int wi = 0; wi < 16; wi++) w[wi] = node_word(L, R, 16 * b + wi);
+    sha256_compress(st, w);
+  }
+  bool rpar = (R[7] & 0xFFu) == 0xFFu;
+#pragma unroll
+  for (int i = 0; i < 7; i++) rpar = rpar && (R[i] == 0xFFFFFFFFu);
+  // out: min from L (bytes 0..28), max from L or R (bytes 29..57)
+#pragma unroll
+  for (int i = 0; i < 7; i++) out[i] = L[i];
+  const uint32_t X7 = rpar ? L[7] : R[7];
+  out[7] = (L[7] & 0xFFu) | (X7 & 0xFFFFFF00u);
+#pragma unroll
+  for (int i = 8; i < 14; i++) out[i] = rpar ? L[i] : R[i];
+  out[14] = (rpar ? L[14] : R[14]) & 0xFFFFu;
+  put_digest(out, st);
+}
+
+// ------------------------------------------------------------------ RFC-6962
+
+// leafHash = SHA256(0x00 || item) for a 90-byte item (2 blocks).
+__device__ __forceinline__ void rfc_leaf90(const uint32_t (&R)[kNodeWords], uint32_t (&st)[8]) {
+  sha256_init(st);
+#pragma unroll
+  for (int b = 0; b < 2; b++) {
+    uint32_t w[16];
+#pragma unroll
+    for (int wi = 0; wi < 16; wi++) {
+      const int q = 16 * b + wi;
+      uint32_t x;
+      if (q == 0) x = perm(0u, R[0], 0x0C000102u);
+      else if (q <= 21) x = perm(R[q - 1], R[q], 0x07000102u);
+      else if (q == 22) x = perm(R[21], R[22], 0x0700010Cu) | 0x80u;
+      else if (q == 31) x = 91u * 8u;
+      else x = 0u;
+      w[wi] = x;
+    }
+    sha256_compress(st, w);
+  }
+}
+
+// innerHash = SHA256(0x01 || l(32) || r(32)) (2 blocks). The DAH tree hashes its levels
+// one after the other in one workgroup (a latency chain), so both compressions are
+// unrolled; the second block's 15 constant words fold into its schedule.
+__device__ __forceinline__ void rfc_inner(const uint32_t* l, const uint32_t* r, uint32_t (&st)[8]) {
+  uint32_t w[16];
+  w[0] = 0x01000000u | (l[0] >> 8);
+#pragma unroll
+  for (int i = 1; i < 8; i++) w[i] = __builtin_amdgcn_alignbit(l[i - 1], l[i], 8);
+  w[8] = __builtin_amdgcn_alignbit(l[7], r[0], 8);
+#pragma unroll
+  for (int i = 9; i < 16; i++) w[i] = __builtin_amdgcn_alignbit(r[i - 9], r[i - 8], 8);
+  sha256_init(st);
+  uint32_t w2[16];
+  w2[0] = (r[7] << 24) | 0x00800000u;
+#pragma unroll
+  for (int i = 1; i < 15; i++) w2[i] = 0;
+  w2[15] = 65u * 8u;
+  sha256_compress(st, w);
+  sha256_compress(st, w2);
+}
+
+}  // namespace cel

@@ -27,6 +27,8 @@
 #include <vector>
 
 #include "../../include/celestia_eds.h"
+#include "blob_plan.hpp"
+#include "square_blobs.hpp"
 
 namespace cel {
 namespace sq {
@@ -38,9 +40,7 @@ constexpr uint32_t kNsIdSize = 28;
 // compact share payload: first share ns | info | sequence length(4) | reserved(4)
 constexpr uint32_t kCompactFirst = kShare - kNs - 1 - 4 - 4;  // 474
 constexpr uint32_t kCompactCont = kShare - kNs - 1 - 4;       // 478
-// sparse share payload: first share ns | info | sequence length(4)
-constexpr uint32_t kSparseFirst = kShare - kNs - 1 - 4;  // 478
-constexpr uint32_t kSparseCont = kShare - kNs - 1;       // 482
+// sparse share payloads (478 first, 482 after): blob_plan.hpp
 
 using Bytes = std::vector<uint8_t>;
 using Ns = std::array<uint8_t, kNs>;
@@ -269,25 +269,11 @@ static uint32_t compact_shares_for(uint64_t seq_bytes) {
   return 1 + (uint32_t)((seq_bytes - kCompactFirst + kCompactCont - 1) / kCompactCont);
 }
 // shares.SparseSharesNeeded
-static uint32_t sparse_shares_for(uint64_t len) {
-  if (len == 0) return 0;
-  if (len <= kSparseFirst) return 1;
-  return 1 + (uint32_t)((len - kSparseFirst + kSparseCont - 1) / kSparseCont);
-}
-static uint32_t pow2ceil(uint64_t n) {
-  uint32_t r = 1;
-  while (r < n) r <<= 1;
-  return r;
-}
-// inclusion.BlobMinSquareSize / SubTreeWidth / NextShareIndex (go-square v1.1.0)
-static uint32_t blob_min_square_size(uint64_t shares) {
-  return pow2ceil((uint64_t)std::ceil(std::sqrt((double)shares)));
-}
-static uint32_t subtree_width(uint32_t shares, uint32_t threshold) {
-  const uint32_t s = pow2ceil((shares + threshold - 1) / threshold);
-  const uint32_t m = blob_min_square_size(shares);
-  return s < m ? s : m;
-}
+static uint32_t sparse_shares_for(uint64_t len) { return (uint32_t)blob::sparse_shares_needed(len); }
+// inclusion.BlobMinSquareSize / SubTreeWidth (blob_plan.hpp) / NextShareIndex (go-square v1.1.0)
+using blob::blob_min_square_size;
+using blob::pow2ceil;
+using blob::subtree_width;
 static uint32_t next_share_index(uint32_t cursor, uint32_t shares, uint32_t threshold) {
   const uint32_t w = subtree_width(shares, threshold);
   return (cursor + w - 1) / w * w;
@@ -470,6 +456,24 @@ struct Builder {
 
 }  // namespace
 }  // namespace sq
+
+bool blob::blob_tx_views(const uint8_t* tx, size_t n, std::vector<View>& out) {
+  const uint8_t* inner;
+  size_t inner_len;
+  std::vector<sq::Blob> blobs;
+  out.clear();
+  if (!sq::unmarshal_blob_tx(tx, n, inner, inner_len, blobs)) return false;
+  for (const sq::Blob& b : blobs) {
+    View v;
+    std::memcpy(v.ns, b.ns.data(), sizeof v.ns);
+    v.data = b.data;
+    v.len = b.len;
+    v.share_version = b.share_version;
+    out.push_back(v);
+  }
+  return true;
+}
+
 }  // namespace cel
 
 namespace {

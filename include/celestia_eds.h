@@ -411,6 +411,51 @@ cel_status cel_get_commitment(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint
                               uint32_t start, uint32_t blob_share_len,
                               uint32_t subtree_root_threshold, uint8_t* commitment);
 
+/* Blob share commitments from blob bytes (go-square v1.1.0 inclusion.CreateCommitment, as
+ * blobtypes.ValidateBlobTx recomputes it for every blob before the square exists,
+ * x/blob/types/blob_tx.go:96-105). The device splits the blobs into sparse shares on the
+ * fly (shares are never written out), hashes the NMT subtree roots of each blob's merkle
+ * mountain range at SubTreeWidth(shares, subtree_root_threshold) and the RFC-6962 root
+ * over them. Only share version 0 exists ("unsupported share version v" otherwise);
+ * namespaces are hashed as given (ValidateBlobNamespace stays with the caller); an empty
+ * blob is CEL_EINVAL ("blob i has no data"), a blob above 2^20 shares CEL_ETOOBIG.
+ *
+ * go-square inclusion.CreateCommitments: blob i is data[offsets[i] .. offsets[i+1]),
+ * namespaces: nblobs*29 (version || id), share_versions nullable (= 0).
+ * commitments: nblobs*32. Page-locked data (cel_host_alloc) is uploaded in place, pageable
+ * data through page-locked staging; large batches run in chunks of whole blobs. */
+cel_status cel_create_commitments(cel_ctx* ctx, const uint8_t* data, const uint64_t* offsets,
+                                  uint32_t nblobs, const uint8_t* namespaces,
+                                  const uint8_t* share_versions, uint32_t subtree_root_threshold,
+                                  uint8_t* commitments);
+/* Same with data and commitments in device memory; offsets / namespaces stay host
+ * (the host plans the leaf slots). Asynchronous on stream. d_work: at least
+ * cel_dev_commitments_workspace_size(sum of the blobs' shares, nblobs) bytes; one call
+ * holds at most 2^31 leaf slots (CEL_ETOOBIG). The kernels read d_data in whole aligned
+ * dwords that hold at least one blob byte, so up to 3 bytes before d_data + offsets[0] and
+ * after the last blob byte are touched (never used): the first and last aligned dword of
+ * the data must be readable, which holds for any hipMalloc'd buffer. */
+size_t cel_dev_commitments_workspace_size(uint64_t total_shares, uint32_t nblobs);
+cel_status cel_dev_create_commitments(cel_ctx* ctx, const void* d_data, const uint64_t* offsets,
+                                      uint32_t nblobs, const uint8_t* namespaces,
+                                      const uint8_t* share_versions, uint32_t subtree_root_threshold,
+                                      void* d_commitments, void* d_work, void* stream);
+/* The block-level shape ProcessProposal needs: every blob of every BlobTx among txs (same tx
+ * encoding and unmarshal rules as cel_square_construct), one device batch. commitments: cap*32,
+ * tx_index[cap] = the tx each blob came from, *n_out = number of blobs (call with cap = 0 to
+ * size; a cap below the count is CEL_EINVAL). The sizing call only counts: an invalid
+ * blob (empty, share version other than 0, above 2^20 shares) is reported by the call
+ * with cap > 0. */
+cel_status cel_blob_tx_commitments(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx_lens,
+                                   uint32_t ntx, uint32_t subtree_root_threshold,
+                                   uint8_t* commitments, uint32_t* tx_index, uint32_t cap,
+                                   uint32_t* n_out);
+/* Host only: MerkleMountainRangeSizes(SparseSharesNeeded(blob_len), SubTreeWidth(...)):
+ * *shares, *width (both nullable), and the subtree sizes (up to cap entries, *n_out = count). */
+cel_status cel_blob_subtree_sizes(uint64_t blob_len, uint32_t subtree_root_threshold,
+                                  uint32_t* shares, uint32_t* width, uint32_t* sizes,
+                                  uint32_t cap, uint32_t* n_out);
+
 /* ---------------------------------------------------- data-square construction
  * go-square v1.1.0 (host code, no device needed):
  *   greedy = 0: square.Construct (app/extend_block.go:16-25, app/process_proposal.go:121-130):
