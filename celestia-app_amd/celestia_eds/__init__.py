@@ -3,7 +3,9 @@
 Python view of libcelestia_eds.so (HIP kernels for gfx950 + C ABI), with the
 reference's package names: `da` (pkg/da), `wrapper` (pkg/wrapper), `rsmt2d`
 (github.com/celestiaorg/rsmt2d), plus `device` for the device-resident batch API
-used by bench.py.
+used by bench.py and `block` for the block path from txs (ExtendBlock, ProcessProposal,
+PrepareProposal over cel_block_extend).
 """
-from . import _lib, da, rsmt2d, wrapper  # noqa: F401
+from . import _lib, block, da, rsmt2d, wrapper  # noqa: F401
 from ._lib import CelError, Context, default_context, load  # noqa: F401
+from .block import ExtendBlock, PrepareProposal, ProcessProposal  # noqa: F401

@@ -72,7 +72,13 @@ void cel_ctx_destroy(cel_ctx* ctx) {
   {
     DeviceGuard g(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (int i = 0; i < 6; i++)
+    if (ctx->ev_sq_done) {
+      (void)hipEventSynchronize(ctx->ev_sq_done);  // a caller stream may still read the square plan
+      (void)hipEventDestroy(ctx->ev_sq_done);
+    }
+    if (ctx->ev_sq_up) (void)hipEventDestroy(ctx->ev_sq_up);
+    if (ctx->sq_stage) (void)hipHostFree(ctx->sq_stage);
+    for (int i = 0; i < cel_ctx::kScratch; i++)
       if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->hstage) (void)hipHostFree(ctx->hstage);
     if (ctx->ev_plan) {

@@ -27,22 +27,23 @@ namespace {
 
 constexpr uint64_t kChunkBytes = 64ull << 20;  // blob bytes per device batch of the host entries
 
-struct Item {
-  const uint8_t* ns;    // 29 bytes
-  const uint8_t* data;  // host bytes (unused by the device-resident entry)
-  uint64_t len;
-};
+using Item = CommitItem;
 
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+}  // namespace
+
+namespace cel {
+namespace abi {
 
 // Workspace for any plan of nblobs blobs with total_shares shares: a blob's alignment gap
 // is below its width, and SubTreeWidth(n) - 1 <= n, so the slots stay below twice the
 // shares (+ one tile of rounding); there is at most one root per share.
-size_t workspace_bound(uint64_t total_shares, uint32_t nblobs) {
+size_t commit_workspace_bound(uint64_t total_shares, uint32_t nblobs) {
   return blob_commit_workspace_size(2 * total_shares + blob::kTile, total_shares, nblobs);
 }
 
-cel_status check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t share_version) {
+cel_status commit_check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t share_version) {
   if (len == 0) return fail(ctx, CEL_EINVAL, "blob " + std::to_string(i) + " has no data");
   if (share_version != 0) return fail(ctx, CEL_EINVAL, "unsupported share version " + std::to_string(share_version));
   if (blob::sparse_shares_needed(len) > blob::kMaxShares)
@@ -50,10 +51,12 @@ cel_status check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t share_ver
   return CEL_OK;
 }
 
-// Plans items [0, nb) whose bytes lie back to back in d_data from base_off on, uploads the
-// tables into d_work's head and enqueues the kernels on s. ctx->mu held, device current.
-cel_status enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const Item* items, uint32_t nb,
-                   uint32_t threshold, uint8_t* d_out, void* d_work, hipStream_t s) {
+// Plans items [0, nb) whose bytes lie in d_data back to back from base_off on (offs ==
+// nullptr) or at byte offsets offs[i], uploads the tables into d_work's head and enqueues the
+// kernels on s. ctx->mu held, device current.
+cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const uint64_t* offs,
+                          const CommitItem* items, uint32_t nb, uint32_t threshold, uint8_t* d_out, void* d_work,
+                          hipStream_t s) {
   hipError_t e;
   if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess)
     return hip_fail(ctx, e, "event");
@@ -65,7 +68,7 @@ cel_status enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const
   plan.recs.reserve(nb);
   uint64_t off = base_off;
   for (uint32_t i = 0; i < nb; i++) {
-    blob::plan_add(plan, items[i].ns, off, items[i].len, threshold);
+    blob::plan_add(plan, items[i].ns, offs ? offs[i] : off, items[i].len, threshold);
     off += items[i].len;
     if (plan.slots + blob::kTile > blob::kMaxSlots)
       return fail(ctx, CEL_ETOOBIG, "too many shares for one device batch");
@@ -115,6 +118,11 @@ bool page_locked(const void* p) {
   return at.type == hipMemoryTypeHost;
 }
 
+}  // namespace abi
+}  // namespace cel
+
+namespace {
+
 // Commitments of host blobs, in chunks of whole blobs of about kChunkBytes. contiguous: the
 // items' bytes lie back to back from items[0].data on (one copy per chunk, straight from
 // the caller's memory if that is page-locked); otherwise each blob is packed into the
@@ -137,7 +145,7 @@ cel_status run_host(cel_ctx* ctx, const std::vector<Item>& items, bool contiguou
     hipError_t e = hipSuccess;
     // + 8: the last dword a lane may touch starts inside the data; keep it inside the buffer
     uint8_t* d_in = static_cast<uint8_t*>(scratch(ctx, S_IN, bytes + 8, &e));
-    void* d_work = scratch(ctx, S_WORK, workspace_bound(shares, nb), &e);
+    void* d_work = scratch(ctx, S_WORK, commit_workspace_bound(shares, nb), &e);
     uint8_t* d_out = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, (size_t)nb * 32, &e));
     if (!d_in || !d_work || !d_out) return fail(ctx, CEL_ENOMEM, "device allocation failed");
     const size_t out_at = direct ? 0 : align256(bytes);
@@ -157,7 +165,7 @@ cel_status run_host(cel_ctx* ctx, const std::vector<Item>& items, bool contiguou
       src = hs;
     }
     if ((e = hipMemcpyAsync(d_in, src, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
-    cel_status st = enqueue(ctx, d_in, 0, items.data() + b0, nb, threshold, d_out, d_work, s);
+    cel_status st = commit_enqueue(ctx, d_in, 0, nullptr, items.data() + b0, nb, threshold, d_out, d_work, s);
     if (st) return st;
     if ((e = hipMemcpyAsync(hs + out_at, d_out, (size_t)nb * 32, hipMemcpyDeviceToHost, s)) != hipSuccess)
       return hip_fail(ctx, e, "D2H");
@@ -179,7 +187,7 @@ cel_status collect(cel_ctx* ctx, const uint8_t* data, const uint64_t* offsets, u
   for (uint32_t i = 0; i < nblobs; i++) {
     if (offsets[i + 1] < offsets[i]) return fail(ctx, CEL_EINVAL, "blob offsets must be non-decreasing");
     const uint64_t len = offsets[i + 1] - offsets[i];
-    cel_status st = check_blob(ctx, i, len, share_versions ? share_versions[i] : 0);
+    cel_status st = commit_check_blob(ctx, i, len, share_versions ? share_versions[i] : 0);
     if (st) return st;
     items[i] = Item{namespaces + (size_t)i * kNs, data + offsets[i], len};
   }
@@ -203,7 +211,7 @@ cel_status cel_create_commitments(cel_ctx* ctx, const uint8_t* data, const uint6
 }
 
 size_t cel_dev_commitments_workspace_size(uint64_t total_shares, uint32_t nblobs) {
-  return workspace_bound(total_shares, nblobs);
+  return commit_workspace_bound(total_shares, nblobs);
 }
 
 cel_status cel_dev_create_commitments(cel_ctx* ctx, const void* d_data, const uint64_t* offsets, uint32_t nblobs,
@@ -217,8 +225,8 @@ cel_status cel_dev_create_commitments(cel_ctx* ctx, const void* d_data, const ui
                           subtree_root_threshold, d_commitments, items);
   if (st) return st;
   DeviceGuard g(ctx->device);
-  return enqueue(ctx, static_cast<const uint8_t*>(d_data), offsets[0], items.data(), nblobs, subtree_root_threshold,
-                 static_cast<uint8_t*>(d_commitments), d_work, pick_stream(ctx, stream));
+  return commit_enqueue(ctx, static_cast<const uint8_t*>(d_data), offsets[0], nullptr, items.data(), nblobs,
+                        subtree_root_threshold, static_cast<uint8_t*>(d_commitments), d_work, pick_stream(ctx, stream));
 }
 
 cel_status cel_blob_tx_commitments(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx,
@@ -247,7 +255,7 @@ cel_status cel_blob_tx_commitments(cel_ctx* ctx, const uint8_t* txs, const uint3
                 "output holds " + std::to_string(cap) + " blobs, the txs carry " + std::to_string(all.size()));
   std::vector<Item> items(all.size());
   for (size_t i = 0; i < all.size(); i++) {
-    cel_status st = check_blob(ctx, (uint32_t)i, all[i].len, all[i].share_version);
+    cel_status st = commit_check_blob(ctx, (uint32_t)i, all[i].len, all[i].share_version);
     if (st) return st;
     items[i] = Item{all[i].ns, all[i].data, all[i].len};
     tx_index[i] = from[i];

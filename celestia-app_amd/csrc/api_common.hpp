@@ -11,7 +11,7 @@
 namespace cel {
 namespace abi {
 
-enum ScratchSlot { S_IN = 0, S_EDS = 1, S_WORK = 2, S_ROOTS = 3, S_AUX = 4, S_MASK = 5 };
+enum ScratchSlot { S_IN = 0, S_EDS = 1, S_WORK = 2, S_ROOTS = 3, S_AUX = 4, S_MASK = 5, S_SQ = 6 };
 
 inline cel_status fail(cel_ctx* ctx, cel_status st, const std::string& msg) {
   if (ctx) ctx->last_error = msg;
@@ -75,6 +75,25 @@ inline hipStream_t pick_stream(cel_ctx* ctx, void* stream) {
   return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 }
 
+
+// Blob share commitments (api_commit.cpp), shared with the block entry point (api_block.cpp).
+struct CommitItem {
+  const uint8_t* ns;    // 29 bytes
+  const uint8_t* data;  // host bytes (unused where the bytes are on the device already)
+  uint64_t len;
+};
+// Is p page-locked host memory (cel_host_alloc, hipHostMalloc / hipHostRegister)?
+bool page_locked(const void* p);
+// "blob i has no data" / "unsupported share version v" / above 2^20 shares.
+cel_status commit_check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t share_version);
+// Workspace for any plan of nblobs blobs with total_shares shares.
+size_t commit_workspace_bound(uint64_t total_shares, uint32_t nblobs);
+// Plans nb blobs whose bytes lie in d_data back to back from base_off on (offs == nullptr) or
+// at byte offsets offs[i]; uploads the plan into d_work's head (through ctx->plan_stage, under
+// its ev_plan rule) and enqueues the kernels on s: 32 bytes per blob into d_out.
+cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const uint64_t* offs,
+                          const CommitItem* items, uint32_t nb, uint32_t threshold, uint8_t* d_out, void* d_work,
+                          hipStream_t s);
 
 inline cel_status validate_square(cel_ctx* ctx, uint32_t k, uint32_t share_size) {
   if (share_size != kShare)

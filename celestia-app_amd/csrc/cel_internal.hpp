@@ -223,6 +223,12 @@ size_t blob_commit_workspace_size(uint64_t slots, uint64_t roots, uint32_t nblob
 hipError_t launch_blob_commit(const uint8_t* d_data, const blob::Plan& plan, void* d_work, uint8_t* d_out,
                               hipStream_t s, uint32_t* d_shares = nullptr);
 
+// The k x k ODS written into quadrant Q0 of d_eds from a layout (square_build.hip): d_segs
+// the segments, d_share_seg the segment index of each of the k * k shares, d_compact the
+// compact shares (16-byte aligned), d_txs the tx bytes the BLOB segments point into.
+hipError_t launch_square_build(const uint8_t* d_txs, const cel_square_segment* d_segs, const uint32_t* d_share_seg,
+                               const uint8_t* d_compact, uint8_t* d_eds, uint32_t k, hipStream_t s);
+
 // Erasure decode of `naxes` axes of 2n shards each, gathered into a dense
 // [naxes][2n][len] buffer with a [naxes][2n] present mask. In place.
 // GF(2^16) erasure decode over n = 512, 1024 or 2048 points (rs_decode_gf16.hip).
@@ -268,8 +274,9 @@ struct cel_ctx {
   cel::DeviceTables tables;
   std::string last_error;
   // Grow-only device scratch (reused across calls on this ctx).
-  void* scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t scratch_size[6] = {0, 0, 0, 0, 0, 0};
+  static constexpr int kScratch = 7;
+  void* scratch[kScratch] = {};
+  size_t scratch_size[kScratch] = {};
   // Grow-only page-locked host staging (the repair's axis lists).
   void* hstage = nullptr;
   size_t hstage_size = 0;
@@ -280,6 +287,14 @@ struct cel_ctx {
   size_t plan_stage_size = 0;
   hipEvent_t ev_plan = nullptr;
   bool plan_pending = false;
+  // The square build's plan (api_block.cpp): page-locked staging under the same rule (the
+  // next call waits for ev_sq_up, recorded after the upload, before refilling it), and the
+  // device copy in scratch slot S_SQ, which k_square_build reads until ev_sq_done: the next
+  // call's stream waits for that event before its upload overwrites the plan.
+  void* sq_stage = nullptr;
+  size_t sq_stage_size = 0;
+  hipEvent_t ev_sq_up = nullptr, ev_sq_done = nullptr;
+  bool sq_pending = false;
   // Schedule fuzzing of the repair's two streams (cel_debug_schedule_fuzz; tests only):
   // before each enqueue point, an idle kernel of 0..fuzz_max_us microseconds.
   uint64_t fuzz_state = 0;

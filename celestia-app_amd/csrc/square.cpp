@@ -8,7 +8,10 @@
 // with the rules of specs/src/specs/shares.md:24-98 (compact and sparse shares),
 // namespace.md:77-84 (reserved namespaces), data_square_layout.md:38-62 (blob
 // placement) and SURVEY.md Appendix A.4. Host code: pure byte layout, sequential by
-// nature and ~1 us per share; the device path starts at the ODS.
+// nature. Builder::export_layout decides where every share goes (segments, start indexes,
+// the compact shares) without touching a blob byte; expand_layout writes the bytes for
+// cel_square_construct, and k_square_build (square_build.hip) writes them on the device
+// from the same layout for cel_block_extend.
 //
 // Builder (go-square square/builder.go): normal txs first, then BlobTxs. Every append
 // is admitted only if the worst-case square still fits maxSquareSize^2:
@@ -315,32 +318,46 @@ static void write_compact(const Ns& ns, const std::vector<Bytes>& units, std::ve
   }
 }
 
-static void write_sparse(const Blob& b, std::vector<uint8_t>& sq) {
+// Sparse shares of one blob, written in place at dst (shares * 512 bytes).
+static void write_sparse(const uint8_t* ns, uint32_t share_version, const uint8_t* data, size_t len, uint8_t* dst) {
   size_t pos = 0;
-  for (bool first = true; pos < b.len; first = false) {
-    uint8_t sh[kShare] = {0};
-    std::memcpy(sh, b.ns.data(), kNs);
-    sh[kNs] = (uint8_t)((b.share_version << 1) | (first ? 1 : 0));
+  for (bool first = true; pos < len; first = false, dst += kShare) {
+    std::memset(dst, 0, kShare);
+    std::memcpy(dst, ns, kNs);
+    dst[kNs] = (uint8_t)((share_version << 1) | (first ? 1 : 0));
     uint32_t header = kNs + 1;
     if (first) {
-      const uint32_t L = (uint32_t)b.len;
-      sh[header] = (uint8_t)(L >> 24), sh[header + 1] = (uint8_t)(L >> 16);
-      sh[header + 2] = (uint8_t)(L >> 8), sh[header + 3] = (uint8_t)L;
+      const uint32_t L = (uint32_t)len;
+      dst[header] = (uint8_t)(L >> 24), dst[header + 1] = (uint8_t)(L >> 16);
+      dst[header + 2] = (uint8_t)(L >> 8), dst[header + 3] = (uint8_t)L;
       header += 4;
     }
-    const size_t n = std::min<size_t>(kShare - header, b.len - pos);
-    std::memcpy(sh + header, b.data + pos, n);
-    sq.insert(sq.end(), sh, sh + kShare);
+    const size_t n = std::min<size_t>(kShare - header, len - pos);
+    std::memcpy(dst + header, data + pos, n);
     pos += n;
   }
 }
 
-static void write_padding(const Ns& ns, uint32_t count, std::vector<uint8_t>& sq) {
-  for (uint32_t i = 0; i < count; i++) {
-    uint8_t sh[kShare] = {0};
-    std::memcpy(sh, ns.data(), kNs);
-    sh[kNs] = 1;  // share version 0, sequence start; sequence length 0
-    sq.insert(sq.end(), sh, sh + kShare);
+static void write_padding(const uint8_t* ns, uint32_t count, uint8_t* dst) {
+  for (uint32_t i = 0; i < count; i++, dst += kShare) {
+    std::memset(dst, 0, kShare);
+    std::memcpy(dst, ns, kNs);
+    dst[kNs] = 1;  // share version 0, sequence start; sequence length 0
+  }
+}
+
+// The bytes of a layout: every segment written at its place in the k * k shares. `base` is
+// the concatenated txs the BLOB segments point into.
+static void expand_layout(const Layout& L, const uint8_t* base, std::vector<uint8_t>& sq) {
+  sq.resize((size_t)L.k * L.k * kShare);
+  for (const cel_square_segment& s : L.segs) {
+    uint8_t* dst = sq.data() + (size_t)s.start * kShare;
+    if (s.kind == CEL_SEG_COMPACT)
+      std::memcpy(dst, L.compact.data() + (size_t)s.off * kShare, (size_t)s.count * kShare);
+    else if (s.kind == CEL_SEG_BLOB)
+      write_sparse(s.ns, s.share_version, base + s.off, s.len, dst);
+    else
+      write_padding(s.ns, s.count, dst);
   }
 }
 
@@ -353,6 +370,7 @@ struct Pfb {
 struct Element {
   Blob blob;
   uint32_t pfb, index, shares;
+  uint32_t tx;  // index of the BlobTx among the block's txs
 };
 
 struct Builder {
@@ -380,7 +398,7 @@ struct Builder {
 
   // Builder.AppendBlobTx: the index wrapper is counted with worst-case share indexes
   // (maxSquareSize^2), each blob with its shares plus SubTreeWidth - 1 of padding.
-  bool append_blob_tx(const uint8_t* inner, size_t n, const std::vector<Blob>& bl) {
+  bool append_blob_tx(const uint8_t* inner, size_t n, const std::vector<Blob>& bl, uint32_t tx_index) {
     const std::vector<uint32_t> worst(bl.size(), max_size * max_size);
     const size_t iw = marshal_index_wrapper(inner, n, worst).size();
     const uint64_t nb = pfb_bytes + uvarint_len(iw) + iw;
@@ -394,43 +412,77 @@ struct Builder {
     pfb_bytes = nb;
     const uint32_t pi = (uint32_t)pfbs.size();
     pfbs.push_back(Pfb{inner, n, std::vector<uint32_t>(bl.size(), 0)});
-    for (uint32_t i = 0; i < bl.size(); i++) blobs.push_back(Element{bl[i], pi, i, sparse_shares_for(bl[i].len)});
+    for (uint32_t i = 0; i < bl.size(); i++) blobs.push_back(Element{bl[i], pi, i, sparse_shares_for(bl[i].len), tx_index});
     return true;
   }
 
-  // Builder.Export
-  uint32_t export_square(std::vector<uint8_t>& sq) {
-    sq.clear();
+  // Builder.Export, the layout only: where every share goes, the start indexes inside the
+  // index wrappers, and the compact shares those wrappers fill. `base`: the concatenated txs
+  // (BLOB segments carry offsets into it). The one walk of cursor / next_share_index /
+  // padding; export_square writes its bytes.
+  void export_layout(const uint8_t* base, Layout& L) {
+    L.compact.clear();
+    L.segs.clear();
+    uint32_t at = 0;  // next share index
+    auto add = [&](uint32_t kind, uint32_t count, const uint8_t* ns) -> cel_square_segment* {
+      if (!count) return nullptr;
+      cel_square_segment s;
+      std::memset(&s, 0, sizeof s);
+      s.kind = kind;
+      s.start = at;
+      s.count = count;
+      if (ns) std::memcpy(s.ns, ns, kNs);
+      at += count;
+      L.segs.push_back(s);
+      return &L.segs.back();
+    };
+    const Ns tail = tail_pad_ns();
     if (txs.empty() && pfbs.empty()) {  // EmptySquare: one tail padding share
-      write_padding(tail_pad_ns(), 1, sq);
-      return 1;
+      add(CEL_SEG_PAD, 1, tail.data());
+      L.k = 1;
+      return;
     }
     const uint32_t k = blob_min_square_size(current);
     std::stable_sort(blobs.begin(), blobs.end(),
                      [](const Element& a, const Element& b) { return a.blob.ns < b.blob.ns; });
     const uint32_t non_reserved = compact_shares_for(tx_bytes) + compact_shares_for(pfb_bytes);
-    uint32_t cursor = non_reserved, end_of_last = non_reserved;
-    std::vector<uint8_t> blob_sq;
+    uint32_t cursor = non_reserved;
+    std::vector<uint32_t> starts(blobs.size());
     for (size_t i = 0; i < blobs.size(); i++) {
       const Element& e = blobs[i];
       cursor = next_share_index(cursor, e.shares, threshold);
-      pfbs[e.pfb].idx[e.index] = cursor;
-      if (i) write_padding(blobs[i - 1].blob.ns, cursor - end_of_last, blob_sq);
-      write_sparse(e.blob, blob_sq);
+      pfbs[e.pfb].idx[e.index] = starts[i] = cursor;
       cursor += e.shares;
-      end_of_last = cursor;
     }
     iws.clear();
     for (const Pfb& p : pfbs) iws.push_back(marshal_index_wrapper(p.tx, p.len, p.idx));
-    write_compact(kTxNs, txs, sq);
-    write_compact(kPfbNs, iws, sq);
-    // WriteSquare: primary reserved padding up to the first blob, the blobs, tail padding
-    const uint32_t first_blob = blobs.empty() ? (uint32_t)(sq.size() / kShare) : pfbs[blobs[0].pfb].idx[blobs[0].index];
-    write_padding(kPrimaryPadNs, first_blob - (uint32_t)(sq.size() / kShare), sq);
-    sq.insert(sq.end(), blob_sq.begin(), blob_sq.end());
-    const uint32_t have = (uint32_t)(sq.size() / kShare);
-    write_padding(tail_pad_ns(), (uint32_t)((uint64_t)k * k - have), sq);
-    return k;
+    write_compact(kTxNs, txs, L.compact);
+    write_compact(kPfbNs, iws, L.compact);
+    // WriteSquare: primary reserved padding up to the first blob, the blobs with namespace
+    // padding (the previous blob's namespace) between them, tail padding
+    const uint32_t ncompact = (uint32_t)(L.compact.size() / kShare);
+    add(CEL_SEG_COMPACT, ncompact, nullptr);
+    add(CEL_SEG_PAD, (blobs.empty() ? ncompact : starts[0]) - ncompact, kPrimaryPadNs.data());
+    for (size_t i = 0; i < blobs.size(); i++) {
+      const Element& e = blobs[i];
+      if (i) add(CEL_SEG_PAD, starts[i] - at, blobs[i - 1].blob.ns.data());
+      if (cel_square_segment* s = add(CEL_SEG_BLOB, e.shares, e.blob.ns.data())) {
+        s->share_version = e.blob.share_version;
+        s->off = (uint64_t)(e.blob.data - base);
+        s->len = (uint32_t)e.blob.len;
+        s->tx_index = e.tx;
+      }
+    }
+    add(CEL_SEG_PAD, (uint32_t)((uint64_t)k * k - at), tail.data());
+    L.k = k;
+  }
+
+  // Builder.Export: the layout, then its bytes.
+  uint32_t export_square(const uint8_t* base, std::vector<uint8_t>& sq) {
+    Layout L;
+    export_layout(base, L);
+    expand_layout(L, base, sq);
+    return L.k;
   }
 
   // Builder.FindTxShareRange (after export_square): the shares [start, end) holding the
@@ -490,7 +542,7 @@ namespace {
 
 // NewBuilder(txs...) / Build's admission loop; fills included[] (0 / 1 normal / 2 blob).
 cel_status build_square(cel::sq::Builder& b, const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx,
-                        uint32_t greedy, uint8_t* included) {
+                        uint32_t greedy, uint8_t* included, std::vector<cel::sq::BlobRef>* all_blobs = nullptr) {
   using namespace cel::sq;
   size_t off = 0;
   bool seen_blob_tx = false;
@@ -505,7 +557,17 @@ cel_status build_square(cel::sq::Builder& b, const uint8_t* txs, const uint32_t*
     const bool is_blob = unmarshal_blob_tx(tx, n, inner, inner_len, blobs);
     if (is_blob) {
       seen_blob_tx = true;
-      ok = b.append_blob_tx(inner, inner_len, blobs);
+      if (all_blobs)
+        for (const Blob& bl : blobs) {
+          BlobRef r;
+          std::memcpy(r.ns, bl.ns.data(), kNs);
+          r.off = bl.len ? (uint64_t)(bl.data - txs) : 0;
+          r.len = bl.len;
+          r.share_version = bl.share_version;
+          r.tx_index = i;
+          all_blobs->push_back(r);
+        }
+      ok = b.append_blob_tx(inner, inner_len, blobs, i);
     } else {
       if (seen_blob_tx && !greedy) {  // square.Construct requires normal txs first
         g_square_error = "normal transaction at index " + std::to_string(i) + " can not be appended after blob tx";
@@ -531,7 +593,51 @@ bool args_ok(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx, uint32_t
 
 }  // namespace
 
+cel_status cel::sq::square_layout(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx, uint32_t max_square_size,
+                                  uint32_t subtree_root_threshold, uint32_t greedy, uint8_t* included, Layout& out,
+                                  std::vector<BlobRef>* all_blobs) {
+  g_square_error.clear();
+  if (!args_ok(txs, tx_lens, ntx, max_square_size, subtree_root_threshold)) {
+    g_square_error = "invalid argument";
+    return CEL_EINVAL;
+  }
+  Builder b(max_square_size, subtree_root_threshold);
+  cel_status st = build_square(b, txs, tx_lens, ntx, greedy, included, all_blobs);
+  if (st) return st;
+  b.export_layout(txs, out);
+  return CEL_OK;
+}
+
 extern "C" {
+
+cel_status cel_square_layout(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx, uint32_t max_square_size,
+                             uint32_t subtree_root_threshold, uint32_t greedy, uint32_t* k_out, uint8_t* included,
+                             cel_square_segment* segments, uint32_t cap_segments, uint32_t* n_segments,
+                             uint8_t* compact_out, uint32_t cap_compact_shares, uint32_t* n_compact_shares) {
+  using namespace cel::sq;
+  if (!k_out || !n_segments || !n_compact_shares || (cap_segments && !segments) ||
+      (cap_compact_shares && !compact_out)) {
+    g_square_error = "invalid argument";
+    return CEL_EINVAL;
+  }
+  Layout L;
+  cel_status st = square_layout(txs, tx_lens, ntx, max_square_size, subtree_root_threshold, greedy, included, L, nullptr);
+  if (st) return st;
+  const uint32_t ncompact = (uint32_t)(L.compact.size() / kShare);
+  *k_out = L.k;
+  *n_segments = (uint32_t)L.segs.size();
+  *n_compact_shares = ncompact;
+  if (cap_segments == 0) return CEL_OK;  // size query
+  if (L.segs.size() > cap_segments || ncompact > cap_compact_shares) {
+    g_square_error = "output holds " + std::to_string(cap_segments) + " segments and " +
+                     std::to_string(cap_compact_shares) + " compact shares, the layout needs " +
+                     std::to_string(L.segs.size()) + " and " + std::to_string(ncompact);
+    return CEL_EINVAL;
+  }
+  std::memcpy(segments, L.segs.data(), L.segs.size() * sizeof(cel_square_segment));
+  if (ncompact) std::memcpy(compact_out, L.compact.data(), L.compact.size());
+  return CEL_OK;
+}
 
 cel_status cel_square_construct(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx, uint32_t max_square_size,
                                 uint32_t subtree_root_threshold, uint32_t greedy, uint8_t* shares_out,
@@ -546,7 +652,7 @@ cel_status cel_square_construct(const uint8_t* txs, const uint32_t* tx_lens, uin
   cel_status st = build_square(b, txs, tx_lens, ntx, greedy, included);
   if (st) return st;
   std::vector<uint8_t> sq;
-  const uint32_t k = b.export_square(sq);
+  const uint32_t k = b.export_square(txs, sq);
   *k_out = k;
   if (!shares_out) return CEL_OK;  // size query
   if ((uint64_t)k * k > cap_shares) {
@@ -573,8 +679,8 @@ cel_status cel_square_tx_range(const uint8_t* txs, const uint32_t* tx_lens, uint
   Builder b(max_square_size, subtree_root_threshold);
   cel_status st = build_square(b, txs, tx_lens, ntx, 0, nullptr);
   if (st) return st;
-  std::vector<uint8_t> sq;
-  b.export_square(sq);
+  Layout L;
+  b.export_layout(txs, L);
   if (!b.tx_range(tx_index, *start, *end)) {
     g_square_error = "txIndex " + std::to_string(tx_index) + " out of range";
     return CEL_EINVAL;

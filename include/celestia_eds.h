@@ -481,8 +481,83 @@ cel_status cel_square_construct(const uint8_t* txs, const uint32_t* tx_lens, uin
 cel_status cel_square_tx_range(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx,
                                uint32_t max_square_size, uint32_t subtree_root_threshold,
                                uint32_t tx_index, uint32_t* start, uint32_t* end);
-/* Message of the last cel_square_construct / cel_square_tx_range failure on this thread. */
+/* Message of the last cel_square_construct / cel_square_tx_range / cel_square_layout failure
+ * on this thread. */
 const char* cel_square_last_error(void);
+
+/* The same square as a layout, without its blob bytes (host only): where every share of the
+ * k*k ODS comes from. The segments are ascending and cover share indices [0, k*k) exactly
+ * once (segments of zero shares are left out):
+ *   CEL_SEG_COMPACT  count shares copied from the compact shares, from share `off` on: the
+ *                    tx and PayForBlob namespaces, whose re-marshalled index wrappers only
+ *                    the host can produce;
+ *   CEL_SEG_BLOB     the count sparse shares of one blob: namespace ns, share version,
+ *                    `len` data bytes at byte `off` of the concatenated txs, from tx tx_index;
+ *   CEL_SEG_PAD      count padding shares of namespace ns (namespace padding between blobs,
+ *                    primary reserved padding, tail padding): ns, info byte 1, zeros. */
+#define CEL_SEG_COMPACT 0u
+#define CEL_SEG_BLOB 1u
+#define CEL_SEG_PAD 2u
+typedef struct cel_square_segment {
+  uint32_t kind;          /* CEL_SEG_* */
+  uint32_t start;         /* first share index of the segment */
+  uint32_t count;         /* shares */
+  uint32_t share_version; /* BLOB: the info byte's version */
+  uint64_t off;           /* COMPACT: share offset in the compact shares; BLOB: byte offset in txs */
+  uint32_t len;           /* BLOB: data bytes */
+  uint32_t tx_index;      /* BLOB: the tx that carries it */
+  uint8_t ns[32];         /* BLOB, PAD: the 29 namespace bytes, then 3 zero bytes */
+} cel_square_segment;
+/* Same inputs, status codes and cel_square_last_error strings as cel_square_construct.
+ * *k_out, included[] (nullable) as there; *n_segments and *n_compact_shares always receive
+ * the counts. cap_segments == 0 only sizes; otherwise segments[cap_segments] and
+ * compact_out[cap_compact_shares * 512] must hold them (CEL_EINVAL if not). */
+cel_status cel_square_layout(const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx,
+                             uint32_t max_square_size, uint32_t subtree_root_threshold,
+                             uint32_t greedy, uint32_t* k_out, uint8_t* included,
+                             cel_square_segment* segments, uint32_t cap_segments,
+                             uint32_t* n_segments, uint8_t* compact_out,
+                             uint32_t cap_compact_shares, uint32_t* n_compact_shares);
+
+/* ------------------------------------------- block data root from txs (one upload)
+ * The block path of app/process_proposal.go:107 (ValidateBlobTx's commitments), :122
+ * (square.Construct), app/prepare_proposal.go:50 (square.Build) and app/extend_block.go:16
+ * (square.Construct + da.ExtendShares) as one call: the host lays the square out
+ * (cel_square_layout), the blob bytes cross PCIe once, the device writes every ODS share
+ * straight into quadrant Q0 of the EDS (blob shares cut from the tx bytes, compact shares
+ * copied, padding shares generated), extends it in place and hashes the roots; the blob
+ * share commitments are hashed from the same device copy of the tx bytes.
+ *
+ * cel_dev_square_build: the device-resident step. d_txs: the concatenated txs in device
+ * memory (the segments' BLOB offsets point into it; aligned dwords that hold at least one
+ * blob byte are read, as cel_dev_create_commitments documents); segments / compact: a
+ * layout of cel_square_layout (host memory); d_eds: an EDS buffer of 2k*2k*512 bytes,
+ * 16-byte aligned, of which exactly quadrant Q0 is written (every byte of it).
+ * Asynchronous on stream (NULL = ctx's stream). */
+cel_status cel_dev_square_build(cel_ctx* ctx, const void* d_txs, const cel_square_segment* segments,
+                                uint32_t n_segments, const uint8_t* compact,
+                                uint32_t n_compact_shares, uint32_t k, void* d_eds, void* stream);
+/* cel_block_extend: txs in, data root (and roots, commitments, optionally the EDS) out.
+ * txs, tx_lens, ntx, max_square_size (up to 512; k >= 256 extends over GF(2^16)),
+ * subtree_root_threshold, greedy, *k_out, included[] (nullable): as cel_square_construct.
+ * row_roots / col_roots: sized for max_square_size (2 * max_square_size * 90 bytes each),
+ * 2k*90 bytes of each are written; dah: 32 bytes. eds_out (nullable) with eds_cap bytes:
+ * the 2k*2k*512-byte EDS (CEL_EINVAL if eds_cap is below that); with CEL_FLAG_PARITY_ONLY
+ * its Q0 cells are not written. commitments / commit_tx_index / commit_cap / n_commit: the
+ * share commitments of every blob of every BlobTx among txs, in order, kept in the square or
+ * not, with cel_blob_tx_commitments' convention (*n_commit always receives the count;
+ * commit_cap == 0 skips them; a cap below the count is CEL_EINVAL). Construction errors are
+ * cel_square_construct's (text in cel_last_error), commitment errors exactly
+ * cel_blob_tx_commitments' (commit_cap > 0 only), both before any device work. Page-locked
+ * txs (cel_host_alloc) are uploaded in place, pageable txs through page-locked staging; with
+ * greedy = 0 only the blob txs (a contiguous tail) are uploaded. */
+cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx_lens, uint32_t ntx,
+                            uint32_t max_square_size, uint32_t subtree_root_threshold,
+                            uint32_t greedy, uint32_t* k_out, uint8_t* included,
+                            uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
+                            uint8_t* eds_out, uint64_t eds_cap, uint8_t* commitments,
+                            uint32_t* commit_tx_index, uint32_t commit_cap, uint32_t* n_commit,
+                            uint32_t flags);
 
 #ifdef __cplusplus
 }
