@@ -443,8 +443,11 @@ __device__ void decode_chunk_gf8p(uint32_t* lds, const uint32_t* err, const uint
 
 // grid: x = axis, y = 64-byte chunk. shards: [naxes][2m][len] in rsmt2d order
 // (data then parity); present: [naxes][2m].
-// GF(2^8) axes the register decoder does not take (2m = 2..256 points; m < 16 or a chunk
-// tail). GF(2^16): rs_decode_gf16.hip.
+// GF(2^8) axes the register decoder does not take: 2m = 2..16 points (m <= 8 data shards).
+// The register decoder (rs_decode_axis.hip) takes 2m = 32..256 at every shard size that is a
+// multiple of 64 (no chunk tail comes here); the wider instantiations below only see an
+// axis of 2 GiB or more, past its 32-bit buffer offsets (rs_decode_axis_supported).
+// GF(2^16): rs_decode_gf16.hip.
 template <uint32_t N8>
 __global__ __launch_bounds__(256) void k_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t m,
                                                    uint32_t len, const uint32_t* __restrict__ tw8,

@@ -376,21 +376,8 @@ def test_dah_hash_any_root_length(ctx):
     counts (data_availability_header.go:92-108: rowsCount row roots, then the first
     rowsCount column roots, nil slices where there are fewer) against a hashlib
     merkle.HashFromByteSlices; 90-byte roots keep going through cel_dah_hash."""
-    import hashlib
     from celestia_eds import da
-
-    def sha(b):
-        return hashlib.sha256(b).digest()
-
-    def rfc(items):
-        if not items:
-            return sha(b"")
-        if len(items) == 1:
-            return sha(b"\x00" + items[0])
-        k = 1
-        while k * 2 < len(items):
-            k *= 2
-        return sha(b"\x01" + rfc(items[:k]) + rfc(items[k:]))
+    from merkle_ref import hash_from_byte_slices as rfc
 
     rng = np.random.default_rng(7)
     cases = [([], []), ([b"a"], [b"b"]), ([b"x" * 32] * 3, [b"y" * 32] * 3), ([b""] * 2, [b"z"] * 2),

@@ -142,6 +142,35 @@ def test_decode_round_trip(oracle, n):
         assert np.array_equal(oracle.rs_decode(sh, present), cw)
 
 
+@pytest.mark.parametrize("simd", [False, True])
+@pytest.mark.parametrize("n", [16, 128, 512, 1024])
+def test_rs_is_independent_per_64_byte_block(oracle, n, simd):
+    """Leopard works on each 64-byte block of the shards on its own (a GF(2^8) symbol is
+    one byte, a GF(2^16) symbol bytes j and j + 32 of a block), so encoding or decoding a
+    64-aligned window of long shards equals the window of the whole result. That ties
+    every shard length to the 64-byte case the Lagrange tests above pin; one n per field
+    path (bit-sliced, GF(2^8), GF(2^16) registers, GF(2^16) LDS on the device), with the
+    SIMD block functions and without."""
+    ln = 2368  # 37 blocks
+    windows = [(0, 64), (64, 128), (0, 2368), (1216, 1280), (2304, 2368), (576, 1728), (64, 2304)]
+    rng = np.random.default_rng(9000 + n)
+    data = rng.integers(0, 256, (n, ln), dtype=np.uint8)
+    present = np.ones(2 * n, np.uint8)
+    present[rng.choice(2 * n, n, replace=False)] = 0
+    oracle.set_simd(simd)
+    try:
+        par = oracle.rs_encode(data)
+        cw = np.concatenate([data, par])
+        damaged = np.where(present[:, None] == 1, cw, 0).astype(np.uint8)
+        whole = oracle.rs_decode(damaged, present)
+        assert np.array_equal(whole, cw)
+        for a, b in windows:
+            assert np.array_equal(oracle.rs_encode(data[:, a:b]), par[:, a:b]), (a, b)
+            assert np.array_equal(oracle.rs_decode(damaged[:, a:b], present), whole[:, a:b]), (a, b)
+    finally:
+        oracle.set_simd(True)
+
+
 def _leopard_decode_py(oracle, shards, present):
     """Pure-Python catid/leopard erasure decoder over GF(2^8) (klauspost leopard8.go
     reconstruct with recoverAll), with the error locator as the direct sum
