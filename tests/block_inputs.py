@@ -106,6 +106,28 @@ def expand(raw, k, segs, compact):
     return out
 
 
+def segment(kind, start, count, ns29, off=0, length=0, share_version=0, tx_index=0):
+    return Segment(kind, start, count, share_version, off, length, tx_index, (ctypes.c_uint8 * 32)(*bytes(ns29)))
+
+
+def blob_layout(lengths, k, seed, version1=()):
+    """A hand-made layout without txs: one random blob per length, back to back in the byte
+    buffer and in the square (share version 1 for the blobs listed in version1), then tail
+    padding to the end of the k x k square. -> (raw bytes, [Segment])"""
+    rng = np.random.default_rng(seed)
+    raw = rng.bytes(int(sum(lengths)))
+    segs, off, start = [], 0, 0
+    for i, n in enumerate(lengths):
+        ns = bytes(19) + rng.integers(0, 256, 10, np.uint8).tobytes()
+        segs.append(segment(SEG_BLOB, start, sparse_shares(n), ns, off, n, 1 if i in version1 else 0))
+        off += n
+        start += sparse_shares(n)
+    assert start <= k * k
+    if start < k * k:
+        segs.append(segment(SEG_PAD, start, k * k - start, TAIL_PAD_NS))
+    return raw, segs
+
+
 def dropping_block():
     """30 blob txs after 4 normal ones: at max_square_size 8 Construct fails at tx 12 and
     Build keeps the first 12."""

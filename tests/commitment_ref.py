@@ -94,6 +94,26 @@ def blob_len_for_shares(n):
     return FIRST + CONT * (n - 1)
 
 
+# --- inputs the commitment tests share ----------------------------------------------------
+
+def random_namespace(rng):
+    """A version-0 namespace: 18 zero bytes, then 10 random ones (rng: numpy Generator)."""
+    return bytes(19) + rng.integers(0, 256, 10, "uint8").tobytes()
+
+
+def random_bytes(rng, n):
+    return rng.integers(0, 256, n, "uint8").tobytes()
+
+
+def rfc_level_sizes(count, lds=1024):
+    """The digest counts of the bottom-up RFC-6962 levels (an unpaired last node moves up)
+    from `count` down to the first that is at most `lds`."""
+    sizes = [count]
+    while sizes[-1] > lds:
+        sizes.append((sizes[-1] + 1) // 2)
+    return sizes
+
+
 # --- the reference-held vector: block 408's blob tx -------------------------------------
 
 def _fields(buf):

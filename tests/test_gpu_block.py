@@ -20,13 +20,16 @@ class Result:
     pass
 
 
-def block_extend(ctx, txs, max_square_size=128, greedy=0, eds="none", cap=None, flags=1):
+def block_extend(ctx, txs, max_square_size=128, greedy=0, eds="none", cap=None, flags=1, txs_at=None):
     """cel_block_extend through the raw ABI. eds: "none" | "full" | "parity" (FLAG_PARITY_ONLY,
     buffer pre-filled with 0x5A); cap: commitment capacity (None = exactly the blob count, 0 =
-    skip). Outputs are sized for max_square_size and pre-filled, so what is written shows."""
+    skip). Outputs are sized for max_square_size and pre-filled, so what is written shows.
+    txs_at: a pointer to a copy of the concatenated txs that the call reads instead."""
     import celestia_eds._lib as L
     l = ctx.lib
     buf, lens, ntx, _ = B.pack(txs)
+    if txs_at is not None:
+        buf = txs_at
     r = Result()
     k, n = ctypes.c_uint32(), ctypes.c_uint32()
     inc = (ctypes.c_uint8 * max(ntx, 1))()

@@ -18,12 +18,7 @@ MIXED_SHARES = [63, 64, 65, 267, 352, 1031, 16384]
 MIXED_LENGTHS = [1, 478, 479, 960, 961] + [ref.blob_len_for_shares(n) for n in MIXED_SHARES]
 
 
-def _ns(rng):
-    return bytes(19) + rng.integers(0, 256, 10, np.uint8).tobytes()
-
-
-def _data(rng, n):
-    return rng.integers(0, 256, n, np.uint8).tobytes()
+_ns, _data = ref.random_namespace, ref.random_bytes
 
 
 def test_block408_signed_commitment(ctx):
