@@ -26,7 +26,7 @@ import ctypes
 
 from . import _lib
 
-RECORD = 96  # 90-byte NMT node + 6 zero bytes (CEL_NODE_RECORD)
+RECORD = 96  # 90-byte NMT node + 6 bytes, zero but for a row subtree's last-leaf mark (CEL_NODE_RECORD)
 
 
 class TorchComm:

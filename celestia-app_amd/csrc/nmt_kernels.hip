@@ -14,7 +14,8 @@
 //              8k^2 x 9. Also checks the honest push order on Q0.
 //   k_level  : one lane per inner node of one tree level, all 4k trees at once.
 //   k_dah    : one workgroup per square, RFC-6962 over the 4k roots.
-// Nodes live on the device as 96-byte records (90 B node + 6 zero bytes) = 24 dwords.
+// Nodes live on the device as 96-byte records (90 B node + 6 zero bytes) = 24 dwords; a
+// slab's row-subtree records carry a mark in dword 23 (k_slab_status).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -456,11 +457,21 @@ __device__ __forceinline__ bool min_below_max(const uint32_t* __restrict__ R, co
   return (r[7] & 0xFFu) < ((l[14] >> 8) & 0xFFu);
 }
 
+// Is the record's minNs (bytes 0..28) the parity namespace 0xFF*29?
+__device__ __forceinline__ bool min_is_parity(const uint32_t* __restrict__ R) {
+  bool par = (R[7] & 0xFFu) == 0xFFu;
+#pragma unroll
+  for (int q = 0; q < 7; q++) par = par && (R[q] == 0xFFFFFFFFu);
+  return par;
+}
+
 // The finish's status in one workgroup: the max over ranks of the gathered step-2 status
 // (first int32 of record r * stride + at), or CEL_EORDER when the push order breaks
-// across a slab boundary in a row of Q0 (rank r's first leaf namespace below rank r-1's
-// last: the subtrees' minNs / maxNs; subs: rank r's 2k row-subtree records at
-// subs[r * stride]).
+// across a slab boundary in a row of Q0: rank r's first leaf namespace (its subtree's
+// minNs) below rank r-1's last leaf namespace. That is r-1's subtree maxNs unless its last
+// leaf carries the parity namespace, which IgnoreMaxNamespace keeps out of maxNs: rank
+// r-1 then set dword 23 of its record (k_slab_status), and any minNs but 0xFF*29 is below
+// it. subs: rank r's 2k row-subtree records at subs[r * stride].
 __global__ __launch_bounds__(256) void k_shard_status(const uint32_t* __restrict__ subs, uint32_t stride, uint32_t at,
                                                       uint32_t k, uint32_t w, uint32_t nranks, int order_check,
                                                       int32_t* __restrict__ status) {
@@ -470,9 +481,11 @@ __global__ __launch_bounds__(256) void k_shard_status(const uint32_t* __restrict
   if (order_check) {
     int mine = 0;
     for (uint32_t i = threadIdx.x; i < k; i += blockDim.x)
-      for (uint32_t r = 1; r < nranks && r * w < k; r++)
-        mine |= min_below_max(subs + ((uint64_t)r * stride + i) * kNodeWords,
-                              subs + ((uint64_t)(r - 1) * stride + i) * kNodeWords);
+      for (uint32_t r = 1; r < nranks && r * w < k; r++) {
+        const uint32_t* R = subs + ((uint64_t)r * stride + i) * kNodeWords;
+        const uint32_t* L = subs + ((uint64_t)(r - 1) * stride + i) * kNodeWords;
+        mine |= L[kNodeWords - 1] ? !min_is_parity(R) : min_below_max(R, L);
+      }
     if (mine) atomicOr(&bad, 1);
   }
   __syncthreads();
@@ -486,8 +499,17 @@ __global__ __launch_bounds__(256) void k_shard_status(const uint32_t* __restrict
   }
 }
 
-__global__ void k_status_from_bad(const int32_t* __restrict__ bad_axis, int32_t* __restrict__ status) {
+// The slab commit's status, and for every Q0 row i whether the slab's last leaf carries the
+// parity namespace: dword 23 of row i's subtree record (record bytes 92..95, past the 90
+// node bytes; no hash or pack reads them) is 1 then and 0 otherwise. k_shard_status needs
+// it: the subtree's maxNs leaves that leaf out.
+__global__ __launch_bounds__(256) void k_slab_status(const int32_t* __restrict__ bad_axis, int32_t* __restrict__ status,
+                                                     const uint32_t* __restrict__ leaves, uint32_t* __restrict__ row_sub,
+                                                     uint32_t k, uint32_t w) {
   if (threadIdx.x == 0) *status = *bad_axis != INT_MAX ? CEL_EORDER : CEL_OK;
+  for (uint32_t i = threadIdx.x; i < k; i += blockDim.x)
+    row_sub[(uint64_t)i * kNodeWords + kNodeWords - 1] =
+        min_is_parity(leaves + ((uint64_t)i * w + w - 1) * kNodeWords) ? 1u : 0u;
 }
 
 __global__ void k_pack_records(const uint32_t* __restrict__ rec, uint32_t n, uint8_t* __restrict__ out) {
@@ -607,7 +629,7 @@ hipError_t launch_slab_leaves(const uint8_t* slab, uint32_t k, uint32_t c0, uint
 
 // After every leaf of the slab: w column trees of 2k leaves (leaf i of column j at
 // i*w + j) and 2k row subtrees of w leaves (leaf j of row i at i*w + j), both sets one
-// level per launch, then the status.
+// level per launch, then the status and the rows' last-leaf marks.
 hipError_t launch_slab_trees(uint32_t k, uint32_t w, uint32_t* col_rec, uint32_t* row_sub, int32_t* status,
                              void* work, hipStream_t s) {
   const uint32_t W = 2 * k;
@@ -620,7 +642,7 @@ hipError_t launch_slab_trees(uint32_t k, uint32_t w, uint32_t* col_rec, uint32_t
   const LevelJob cols{sw.leaves, nullptr, W, w, 1, w};
   const LevelJob rows{sw.leaves, nullptr, w, W, w, 1};
   reduce_grid_pair(cols, sw.ping, sw.pong, col_rec, rows, sw.ping2, sw.pong2, row_sub, s);
-  hipLaunchKernelGGL(k_status_from_bad, dim3(1), dim3(64), 0, s, sw.bad, status);
+  hipLaunchKernelGGL(k_slab_status, dim3(1), dim3(256), 0, s, sw.bad, status, sw.leaves, row_sub, k, w);
   return hipGetLastError();
 }
 

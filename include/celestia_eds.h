@@ -149,7 +149,10 @@ cel_status cel_dev_commit_only(cel_ctx* ctx, const void* d_eds, uint32_t n, uint
  * all-to-all of cells, one all-gather of node records) belong to the caller (RCCL
  * through torch.distributed); these calls are the per-rank device steps.
  * Supported for k in {256, 512} (Leopard GF(2^16)), nranks a power of two <= k.
- * Node records are 96 bytes: the 90-byte NMT node and 6 zero bytes. */
+ * Node records are 96 bytes: the 90-byte NMT node and 6 zero bytes. In a row-subtree
+ * record of a Q0 row, bytes 92..95 are a little-endian 1 when the slab's last leaf in that
+ * row carries the parity namespace 0xFF*29 (IgnoreMaxNamespace keeps it out of the
+ * subtree's maxNs, and step 3's push-order check across slab boundaries needs it). */
 #define CEL_NODE_RECORD 96u
 size_t cel_dev_shard_workspace_size(uint32_t k, uint32_t nranks);
 /* Step 1: row-encode this rank's k/nranks ODS rows (d_ods_rows: [k/nranks][k][512])

@@ -23,6 +23,18 @@ def constant_ods(k):
     return np.frombuffer(sh * (k * k), np.uint8).reshape(k, k, SHARE).copy()
 
 
+def parity_before_boundary_ods(k, col, seed=0):
+    """A square whose row 0 is `A .. A, 0xFF*29 | B .. B` with the bar before column `col`
+    and A <= B < 0xFF*29; every other row carries 0xFF*29 throughout, so every column stays
+    ordered and only row 0 breaks the push order (B after 0xFF*29)."""
+    assert 2 <= col < k
+    ods = np.random.default_rng(seed).integers(0, 256, (k, k, SHARE), dtype=np.uint8)
+    ods[:, :, :NS] = 0xFF
+    ods[0, :col - 1, :NS] = 0x10
+    ods[0, col:, :NS] = 0x20
+    return ods
+
+
 def tail_padding_share():
     sh = b"\xff" * 28 + b"\xfe" + b"\x01" + bytes(4)
     return sh + bytes(SHARE - len(sh))

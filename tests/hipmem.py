@@ -46,6 +46,13 @@ class DeviceBuffer:
         assert a.nbytes <= self.nbytes
         _ck(hip().hipMemcpy(self.ptr, a.ctypes.data_as(ctypes.c_void_p), a.nbytes, _H2D), "H2D")
 
+    def upload_at(self, offset, arr):
+        """H2D of arr's bytes to `offset` bytes into the buffer."""
+        a = np.ascontiguousarray(arr)
+        assert 0 <= offset and offset + a.nbytes <= self.nbytes
+        dst = ctypes.c_void_p(self.ptr.value + offset)
+        _ck(hip().hipMemcpy(dst, a.ctypes.data_as(ctypes.c_void_p), a.nbytes, _H2D), "H2D")
+
     def upload_async(self, arr, stream):
         """H2D on `stream` (ordered after the stream's earlier work); `arr` must stay alive
         until the stream is synchronized."""

@@ -15,6 +15,7 @@ import oracle
 NS = 29
 PARITY_NS = b"\xff" * NS
 EORDER = 5
+LAST_PARITY = 92  # record byte past the 90-byte node: "the slab's last leaf has the parity namespace"
 
 
 def record(node90: bytes) -> np.ndarray:
@@ -61,7 +62,11 @@ class OracleSteps:
                 leaves.append(ns + cell)
             rc, root = oracle.nmt_root(leaves, self.order_check)
             bad |= rc != 0
-            row_sub[i] = torch.from_numpy(record(root).copy())
+            rec = record(root).copy()
+            # a Q0 row whose last leaf in this slab has the parity namespace: IgnoreMaxNamespace
+            # keeps it out of the subtree's maxNs, so the record's tail says it (dword 23)
+            rec[LAST_PARITY] = 1 if (i < k and leaves[-1][:NS] == PARITY_NS) else 0
+            row_sub[i] = torch.from_numpy(rec)
         status[0] = EORDER if bad else 0
 
     def finish(self, gathered, k, n, row_roots, col_roots, dah, status):
@@ -74,8 +79,9 @@ class OracleSteps:
         for i in range(2 * k):
             nodes = [subs[r, i, :90].tobytes() for r in range(n)]
             if self.order_check and i < k:
-                for r in range(1, n):
-                    if r * w < k and nodes[r][:NS] < nodes[r - 1][NS:2 * NS]:
+                for r in range(1, n):  # rank r's first leaf against rank r-1's last leaf
+                    last = PARITY_NS if subs[r - 1, i, LAST_PARITY] else nodes[r - 1][NS:2 * NS]
+                    if r * w < k and nodes[r][:NS] < last:
                         bad = True
             while len(nodes) > 1:
                 nodes = [hash_node(nodes[2 * j], nodes[2 * j + 1]) for j in range(len(nodes) // 2)]

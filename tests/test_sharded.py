@@ -107,6 +107,35 @@ def test_one_rank_aliases_slab(oracle, local):
     assert sq.dah.numpy().tobytes() == dah
 
 
+@pytest.mark.parametrize("k,n,col", [(4, 4, 2), (8, 8, 2), (8, 8, 4), (8, 8, 6), (8, 4, 4)])
+def test_parity_namespace_before_slab_boundary(oracle, k, n, col):
+    """Row 0 is `A .. A, 0xFF*29 | B ..` with the bar on a slab boundary inside Q0 and
+    A <= B < 0xFF*29: nmt's Push refuses B after 0xFF*29, and the whole-square oracle says
+    so. Every slab is ordered inside, and IgnoreMaxNamespace makes the left slab's subtree
+    maxNs A, not 0xFF*29, so the finish has to know the slab's last leaf, not its maxNs.
+    The same row with 0xFF*29 after the bar as well is in order."""
+    from celestia_eds.sharded import LocalComm, ShardedSquare
+    from eds_inputs import parity_before_boundary_ods
+    from sharded_oracle import EORDER, OracleSteps
+    assert col % (2 * k // n) == 0
+    bad = parity_before_boundary_ods(k, col)
+    ok = bad.copy()
+    ok[0, col:, :29] = 0xFF
+    for ods, want in ((bad, EORDER), (ok, 0)):
+        assert oracle.roots(oracle.extend(ods), check_order=True)[0] == want
+        squares = [ShardedSquare(k, r, n, OracleSteps()) for r in range(n)]
+        for s in squares:
+            a, b = s.row_range()
+            s.ods_rows.copy_(torch.from_numpy(np.ascontiguousarray(ods[a:b])))
+        LocalComm.run(squares)
+        assert [int(s.status.item()) for s in squares] == [want] * n
+        if want == 0:
+            _, rr, cr, dah = oracle.extend_and_commit(ods, want_eds=False)
+            for s in squares:
+                assert np.array_equal(s.row_roots.numpy(), rr) and np.array_equal(s.col_roots.numpy(), cr)
+                assert s.dah.numpy().tobytes() == dah
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,n", [(256, 1), (256, 2), (256, 8), (512, 4), (512, 8)])
 def test_device_sharded_local(ctx, oracle, k, n):
