@@ -175,7 +175,7 @@ static PipePlan pipe_plan(uint32_t k, uint32_t n) {
   size_t off = 0;
   for (uint32_t c = 0; c < p.nchunks; c++) {
     p.work_off[c] = off;
-    off += (nmt_workspace_size(k, p.cnt[c]) + 255) & ~(size_t)255;
+    off += align256(nmt_workspace_size(k, p.cnt[c]));
   }
   p.work_bytes = off;
   return p;

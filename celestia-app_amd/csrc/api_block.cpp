@@ -25,8 +25,6 @@ using namespace cel::abi;
 
 namespace {
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 // A caller's layout: ascending segments that cover [0, k * k) exactly once, compact reads
 // inside the compact shares, blob segments as long as their blob.
 cel_status check_layout(cel_ctx* ctx, const cel_square_segment* segs, uint32_t nseg, uint32_t ncompact, uint32_t k,

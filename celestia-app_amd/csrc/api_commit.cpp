@@ -29,8 +29,6 @@ constexpr uint64_t kChunkBytes = 64ull << 20;  // blob bytes per device batch of
 
 using Item = CommitItem;
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
 }  // namespace
 
 namespace cel {
@@ -74,6 +72,7 @@ cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off
       return fail(ctx, CEL_ETOOBIG, "too many shares for one device batch");
   }
   const uint64_t slots = (plan.slots + blob::kTile - 1) / blob::kTile * blob::kTile;
+  // the head of blob_work's layout (blob_commit.hip): the records, then the slot table
   const size_t rec_bytes = align256((size_t)nb * sizeof(blob::Rec));
   const size_t bytes = rec_bytes + slots * 4;
   if (ctx->plan_stage_size < bytes) {

@@ -541,6 +541,10 @@ static SweepPlan plan_sweeps(const std::vector<uint8_t>& hm, uint32_t k) {
   return p;
 }
 
+// Where repair_exact keeps its root records in b.work: after the axes-roots workspace of
+// one direction's 2k axes (repair_bufs sizes b.work to hold both).
+static size_t exact_rec_offset(uint32_t k) { return align256(axes_roots_workspace_size(k, 2 * k)); }
+
 static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>& hm, uint32_t k,
                                const uint8_t* row_roots, const uint8_t* col_roots, const RepairOut& out) {
   const Range range("repair.exact");
@@ -556,10 +560,9 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
   for (size_t o = 0; o < order.size(); o++)
     if (order[o].kind == Check::SOLVE) first[(size_t)order[o].solve] = o;
   const bool in_square = rs_decode_axis_supported(W, kShare);
-  // roots of the checked axes: 96-byte records after the axes-roots workspace (b.work holds
-  // the whole-square commit's workspace, which is larger)
-  const size_t ws_axes = (axes_roots_workspace_size(k, W) + 255) & ~(size_t)255;
-  uint32_t* d_rec = reinterpret_cast<uint32_t*>(b.work + ws_axes);
+  // roots of the checked axes: 96-byte records after the axes-roots workspace (repair_bufs
+  // sizes b.work for both)
+  uint32_t* d_rec = reinterpret_cast<uint32_t*>(b.work + exact_rec_offset(k));
   std::vector<uint8_t> h_rec((size_t)2 * W * kNodeWords * 4);
   std::vector<int32_t> h_flags((size_t)2 * W);
   hipError_t e;
@@ -714,7 +717,7 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
     for (; j < W; j++) c += r[j];
     if (c >= k && c < W) first.push_back((int32_t)i);
   }
-  const size_t cells_a = (cells + 255) & ~(size_t)255;
+  const size_t cells_a = align256(cells);
   std::memcpy(b.hmask, hm.data(), cells);
   if (!first.empty()) std::memcpy(b.hmask + cells_a, first.data(), first.size() * 4);
   // the flags are the side stream's (its checks), zeroed there after the mask is up
@@ -823,16 +826,19 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
 static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs* b) {
   const uint32_t W = 2 * k;
   const size_t cells = (size_t)W * W, eds_b = cells * kShare;
-  const size_t cells_a = (cells + 255) & ~(size_t)255;
+  const size_t cells_a = align256(cells);
   hipError_t e = hipSuccess;
   b->W = W;
   if (own_eds) b->eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, eds_b, &e));
   b->dense[0] = static_cast<uint8_t*>(scratch(ctx, S_IN, 3 * eds_b, &e));
   b->tmp = static_cast<uint8_t*>(scratch(ctx, S_AUX, eds_b / 2 + (size_t)kIdxSlots * W * 4 + 256, &e));
-  const size_t list_a = ((size_t)W * 4 + 255) & ~(size_t)255;
+  const size_t list_a = align256((size_t)W * 4);
   b->mask = static_cast<uint8_t*>(scratch(ctx, S_MASK, 3 * cells_a + list_a, &e));
-  b->work = static_cast<uint8_t*>(scratch(ctx, S_WORK, nmt_workspace_size(k, 1), &e));
-  const size_t roots_a = (2 * (size_t)W * kNode + 255) & ~(size_t)255;
+  // the whole-square commit's workspace, or repair_exact's: the axes-roots workspace of one
+  // direction's axes, then the root records of both directions
+  const size_t work_b = std::max(nmt_workspace_size(k, 1), exact_rec_offset(k) + 2 * (size_t)W * kNodeWords * 4);
+  b->work = static_cast<uint8_t*>(scratch(ctx, S_WORK, work_b, &e));
+  const size_t roots_a = align256(2 * (size_t)W * kNode);
   b->res_bytes = roots_a + 2 * (size_t)W * 4;
   b->roots = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, b->res_bytes, &e));
   if (!b->eds || !b->dense[0] || !b->tmp || !b->mask || !b->work || !b->roots)
@@ -844,7 +850,7 @@ static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs
   b->dmask_chk = b->dmask + cells_a;
   b->flags = reinterpret_cast<int32_t*>(b->roots + roots_a);
   b->idx = reinterpret_cast<int32_t*>(b->tmp + eds_b / 2);
-  const size_t cells_h = (cells + 255) & ~(size_t)255;
+  const size_t cells_h = align256(cells);
   // axis lists, mask + first list, results
   const size_t hb = (size_t)kIdxSlots * W * 4 + cells_h + list_a + b->res_bytes;
   if (!host_stage(ctx, hb)) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");

@@ -206,10 +206,8 @@ __global__ __launch_bounds__(256) void k_blob_tile(const uint8_t* __restrict__ d
     if (tid < (256u >> L)) {
       const uint32_t t = tid << L, m = meta[t];
       if ((m >> 24) >= L && (m & 0xFFFFFFu) >= (1u << L)) {
-        uint32_t l[kNodeWords], r[kNodeWords], o[kNodeWords];
-        load_node(nodes + t * kNodeWords, l);
-        load_node(nodes + (t + (1u << (L - 1))) * kNodeWords, r);
-        hash_node(l, r, o);
+        uint32_t o[kNodeWords];
+        hash_pair(nodes, t, t + (1u << (L - 1)), o);
         store_node(nodes + t * kNodeWords, o);
       }
     }
@@ -241,10 +239,8 @@ __global__ __launch_bounds__(256) void k_blob_top_level(const Rec* __restrict__ 
   if (b == kNoBlob) return;
   const Rec* r = recs + b;
   if (r->wlog < L || r->n - (slot - r->first) < (1u << L)) return;
-  uint32_t l[kNodeWords], rr[kNodeWords], o[kNodeWords];
-  load_node(tops + tile * kNodeWords, l);
-  load_node(tops + (tile + (1u << (L - 9))) * kNodeWords, rr);
-  hash_node(l, rr, o);
+  uint32_t o[kNodeWords];
+  hash_pair(tops, tile, tile + (1u << (L - 9)), o);
   store_node(tops + tile * kNodeWords, o);
 }
 
@@ -338,13 +334,31 @@ __global__ __launch_bounds__(256) void k_blob_commit(const Rec* __restrict__ rec
   }
 }
 
-size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+// Workspace: the plan's tables (nblobs records | slot table [slots], uploaded by the caller) |
+//            tile tops [slots / 256] nodes | roots [roots] nodes | da, db [roots][8]
+struct BlobWork {
+  const Rec* recs;
+  const uint32_t* slot_blob;
+  uint32_t *tops, *roots, *da, *db;
+  size_t size;
+};
+BlobWork blob_work(void* work, uint64_t slots, uint64_t roots, uint32_t nblobs) {
+  Carver c(work);
+  BlobWork w;
+  w.recs = c.take<const Rec>((size_t)nblobs * sizeof(Rec));
+  w.slot_blob = c.take<const uint32_t>(slots * 4);
+  w.tops = c.take<uint32_t>(slots / 256 * kNodeWords * 4);
+  w.roots = c.take<uint32_t>(roots * kNodeWords * 4);
+  w.da = c.take<uint32_t>(roots * 32);
+  w.db = c.take<uint32_t>(roots * 32);
+  w.size = c.size();
+  return w;
+}
 
 }  // namespace
 
 size_t blob_commit_workspace_size(uint64_t slots, uint64_t roots, uint32_t nblobs) {
-  return align256((size_t)nblobs * sizeof(Rec)) + align256(slots * 4) + align256(slots / 256 * kNodeWords * 4) +
-         align256(roots * kNodeWords * 4) + 2 * align256(roots * 32);
+  return blob_work(nullptr, slots, roots, nblobs).size;
 }
 
 // tables: nblobs records then, 256-aligned, the slot table (plan.slots entries), already
@@ -354,31 +368,22 @@ hipError_t launch_blob_commit(const uint8_t* d_data, const blob::Plan& plan, voi
                               hipStream_t s, uint32_t* d_shares) {
   const uint32_t nblobs = (uint32_t)plan.recs.size();
   const uint32_t tiles = (uint32_t)(plan.slots / 256);
-  uint8_t* p = static_cast<uint8_t*>(d_work);
-  const Rec* recs = reinterpret_cast<const Rec*>(p);
-  p += align256((size_t)nblobs * sizeof(Rec));
-  const uint32_t* slot_blob = reinterpret_cast<const uint32_t*>(p);
-  p += align256(plan.slots * 4);
-  uint32_t* tops = reinterpret_cast<uint32_t*>(p);
-  p += align256((size_t)tiles * kNodeWords * 4);
-  uint32_t* roots = reinterpret_cast<uint32_t*>(p);
-  p += align256(plan.roots * kNodeWords * 4);
-  uint32_t* da = reinterpret_cast<uint32_t*>(p);
-  uint32_t* db = reinterpret_cast<uint32_t*>(p + align256(plan.roots * 32));
+  const BlobWork w = blob_work(d_work, plan.slots, plan.roots, nblobs);
   if (d_shares) {
-    k_blob_expand<<<tiles * 128, 256, 0, s>>>(d_data, recs, slot_blob, d_shares);
-    k_blob_tile<true><<<tiles, 256, 0, s>>>(d_data, recs, slot_blob, roots, tops, d_shares);
+    k_blob_expand<<<tiles * 128, 256, 0, s>>>(d_data, w.recs, w.slot_blob, d_shares);
+    k_blob_tile<true><<<tiles, 256, 0, s>>>(d_data, w.recs, w.slot_blob, w.roots, w.tops, d_shares);
   } else {
-    k_blob_tile<false><<<tiles, 256, 0, s>>>(d_data, recs, slot_blob, roots, tops, nullptr);
+    k_blob_tile<false><<<tiles, 256, 0, s>>>(d_data, w.recs, w.slot_blob, w.roots, w.tops, nullptr);
   }
   for (uint32_t L = 9; L <= plan.max_wlog; L++) {
     const uint32_t lanes = (tiles + (1u << (L - 8)) - 1) >> (L - 8);
-    k_blob_top_level<<<(lanes + 255) / 256, 256, 0, s>>>(recs, slot_blob, tops, tiles, L);
+    k_blob_top_level<<<(lanes + 255) / 256, 256, 0, s>>>(w.recs, w.slot_blob, w.tops, tiles, L);
   }
-  if (plan.max_wlog > 8) k_blob_top_roots<<<(tiles + 255) / 256, 256, 0, s>>>(recs, slot_blob, tops, roots, tiles);
+  if (plan.max_wlog > 8)
+    k_blob_top_roots<<<(tiles + 255) / 256, 256, 0, s>>>(w.recs, w.slot_blob, w.tops, w.roots, tiles);
   // one lane per pair of the widest RFC level where that keeps a wave busy
   const uint32_t block = plan.max_roots <= 128 ? 64u : 256u;
-  k_blob_commit<<<nblobs, block, 0, s>>>(recs, roots, da, db, d_out);
+  k_blob_commit<<<nblobs, block, 0, s>>>(w.recs, w.roots, w.da, w.db, d_out);
   return hipGetLastError();
 }
 

@@ -62,6 +62,25 @@ struct DeviceTables {
   uint16_t* tower16 = nullptr; // [256 + 256 + 16] Cantor -> tower coordinates (lo, hi byte), b_i (decoder)
 };
 
+// Every workspace region starts on a 256-byte boundary.
+constexpr size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// Bump-carver of a workspace: take<T>(bytes) returns the next region and advances by
+// align256(bytes). Each path carves its workspace in one function; run on a null base
+// (every pointer null, no arithmetic on it) the same function gives the workspace's size.
+struct Carver {
+  uint8_t* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base(static_cast<uint8_t*>(b)) {}
+  template <class T>
+  T* take(size_t bytes) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align256(bytes);
+    return p;
+  }
+  size_t size() const { return off; }
+};
+
 // Block size 2^J of the GF(2^16) decoder's products by twiddles below 2^r (Cantor
 // representation): such a twiddle lies in GF(2^(2^J)), the smallest Cantor subfield holding
 // span(beta_0 .. beta_{r-1}).
@@ -90,7 +109,9 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb) {
 hipError_t upload_tables(DeviceTables* t);
 void free_tables(DeviceTables* t);
 
-// Kernel launchers (rs_kernels.hip / nmt_kernels.hip). All asynchronous on `s`.
+// Kernel launchers (the rs_*.hip files; nmt_kernels.hip the EDS commit, nmt_slab.hip the
+// row-sharded mode, nmt_trees.hip single trees, axes roots, exported trees and byte slices).
+// All asynchronous on `s`.
 hipError_t launch_rs_encode(const RsGeom& g, const DeviceTables& t, hipStream_t s);
 hipError_t launch_rs_encode_bitslice(const RsGeom& g, hipStream_t s);  // GF(2^8), n <= 16
 hipError_t launch_rs_encode_axis(const RsGeom& g, hipStream_t s);       // GF(2^8), 32 <= n <= 128
@@ -183,7 +204,7 @@ hipError_t launch_probe_rs_transform(uint32_t k, const uint32_t* src, uint32_t* 
 hipError_t launch_probe_rs_transform_gf16(uint32_t k, const uint8_t* src, uint8_t* dst, uint32_t ntiles,
                                           hipStream_t s);
 
-// Repair helpers (repair_kernels.hip, nmt_kernels.hip).
+// Repair helpers (repair_kernels.hip, nmt_trees.hip).
 hipError_t launch_gather_axes(const uint8_t* eds, const uint8_t* mask, uint32_t W, const int32_t* idx, int is_col,
                               uint32_t naxes, uint8_t* dense, uint8_t* dmask, hipStream_t s);
 hipError_t launch_scatter_axes(uint8_t* eds, uint8_t* mask, uint32_t W, const int32_t* idx, int is_col,

@@ -1,7 +1,9 @@
 // Device building blocks of the NMT and RFC-6962 hashing shared by nmt_kernels.hip (the EDS
-// commit) and blob_commit.hip (blob share commitments): 96-byte node records, the leaf hash
-// of a 512-byte share, HashNode with IgnoreMaxNamespace, and the RFC-6962 leaf / inner
-// hashes. One message per lane.
+// commit), nmt_slab.hip (the row-sharded mode), nmt_trees.hip (single trees, axes roots,
+// exported trees) and blob_commit.hip (blob share commitments): 96-byte node records, the
+// leaf hash of a 512-byte share, the namespace compares, HashNode with IgnoreMaxNamespace,
+// the inner-node step of a tree level (hash_pair), and the RFC-6962 leaf / inner hashes.
+// One message per lane.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -155,6 +157,35 @@ __device__ __forceinline__ void make_leaf_node(const uint32_t* __restrict__ sh, 
   put_digest(nd, st);
 }
 
+// Namespace order: is ns(a) < ns(b)? (29-byte lexicographic compare of share prefixes)
+__device__ __forceinline__ bool ns_less(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b) {
+  const uint4* pa = reinterpret_cast<const uint4*>(a);
+  const uint4* pb = reinterpret_cast<const uint4*>(b);
+  uint32_t x[8], y[8];
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const uint4 u = pa[i], v = pb[i];
+    x[4 * i] = u.x; x[4 * i + 1] = u.y; x[4 * i + 2] = u.z; x[4 * i + 3] = u.w;
+    y[4 * i] = v.x; y[4 * i + 1] = v.y; y[4 * i + 2] = v.z; y[4 * i + 3] = v.w;
+  }
+  int res = 0;  // -1 a<b, 1 a>b
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint32_t xa = bswap32(x[i]), yb = bswap32(y[i]);
+    if (i == 7) { xa &= 0xFF000000u; yb &= 0xFF000000u; }
+    if (res == 0 && xa != yb) res = xa < yb ? -1 : 1;
+  }
+  return res < 0;
+}
+
+// Is the record's minNs (bytes 0..28) the parity namespace 0xFF*29?
+__device__ __forceinline__ bool min_is_parity(const uint32_t* __restrict__ R) {
+  bool par = (R[7] & 0xFFu) == 0xFFu;
+#pragma unroll
+  for (int q = 0; q < 7; q++) par = par && (R[q] == 0xFFFFFFFFu);
+  return par;
+}
+
 // ---------------------------------------------------------------- inner nodes
 
 // HashNode(L, R): message 0x01 || L(90) || R(90) = 181 B -> 3 blocks.
@@ -218,7 +249,25 @@ __device__ __forceinline__ void hash_node(const uint32_t (&L)[kNodeWords], const
   put_digest(out, st);
 }
 
+// The inner-node step of every tree level: o = HashNode(in[li], in[ri]), li / ri in records.
+__device__ __forceinline__ void hash_pair(const uint32_t* in, uint64_t li, uint64_t ri, uint32_t (&o)[kNodeWords]) {
+  uint32_t L[kNodeWords], R[kNodeWords];
+  load_node(in + li * kNodeWords, L);
+  load_node(in + ri * kNodeWords, R);
+  hash_node(L, R, o);
+}
+
 // ------------------------------------------------------------------ RFC-6962
+
+// SHA256 of the empty string (RFC-6962 empty tree).
+__device__ __forceinline__ void sha_empty(uint32_t (&st)[8]) {
+  uint32_t w[16];
+  w[0] = 0x80000000u;
+#pragma unroll
+  for (int i = 1; i < 16; i++) w[i] = 0;
+  sha256_init(st);
+  sha256_compress(st, w);
+}
 
 // leafHash = SHA256(0x00 || item) for a 90-byte item (2 blocks).
 __device__ __forceinline__ void rfc_leaf90(const uint32_t (&R)[kNodeWords], uint32_t (&st)[8]) {

@@ -24,7 +24,7 @@ srcs=$(sed -n 's/^SRC := //p' celestia-app_amd/Makefile | sed 's#csrc/##g')
 objs=""
 for f in $srcs; do
   extra=""
-  [ "$f" = nmt_kernels.hip ] && extra="-mllvm -amdgpu-sched-strategy=max-memory-clause"
+  case $f in nmt_kernels.hip|nmt_slab.hip|nmt_trees.hip) extra="-mllvm -amdgpu-sched-strategy=max-memory-clause";; esac
   $HIPCC --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $extra $flags -x hip \
     -I$bd/include -c $bd/src/csrc/$f -o $bd/$f.o &
   objs="$objs $bd/$f.o"
