@@ -134,12 +134,14 @@ hipError_t launch_extend_rows(uint8_t* eds, uint32_t k, uint32_t row0, uint32_t 
                               hipStream_t s, const uint8_t* ods = nullptr);
 hipError_t launch_extend_cols(uint8_t* eds, uint32_t k, uint32_t nsq, const DeviceTables& t, hipStream_t s);
 
-// NMT + DAH over resident EDSs. work: scratch of nmt_workspace_size(k, nsq) bytes.
+// NMT + DAH over resident EDSs. work: scratch of nmt_workspace_size(k, nsq) bytes; its
+// carve-up is nmt_kernels.hip's own. A batch (nsq > 1) hashes leaves and level 1 in one
+// kernel and has no leaf area; one square keeps leaf records (the two-step commit below).
 size_t nmt_workspace_size(uint32_t k, uint32_t nsq);
 hipError_t launch_commit(const uint8_t* eds, uint32_t k, uint32_t nsq, uint8_t* row_roots,
                          uint8_t* col_roots, uint8_t* dah, int32_t* status, void* work,
                          bool order_check, hipStream_t s);
-// The same commit in two steps: the leaves of EDS rows [row0, row1) of every square
+// One square's commit (nsq == 1) in two steps: the leaves of EDS rows [row0, row1)
 // (init_bad: reset the push-order flags first; it must precede every leaf launch of the
 // commit in stream order), then, after every leaf, the tree levels, roots and DAH.
 hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, void* work, bool order_check,

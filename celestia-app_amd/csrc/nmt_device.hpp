@@ -132,12 +132,11 @@ __device__ __forceinline__ void leaf_hash(uint32_t (&st)[8], const uint32_t* __r
   }
 }
 
-// Leaf node of one EDS cell: ns || ns || SHA256(0x00 || ns || share), ns = share[0:29]
-// for Q0 cells and 0xFF*29 (parity namespace) otherwise.
-template <bool PF>
-__device__ __forceinline__ void make_leaf_node(const uint32_t* __restrict__ sh, bool q0, uint32_t (&nd)[kNodeWords]) {
-  uint32_t st[8];
-  leaf_hash<PF>(st, sh, q0);
+// The leaf record of one EDS cell from its leaf digest st: ns || ns || digest. The
+// namespaces come from the share again (32 bytes), so a caller that keeps a leaf across
+// other hashes holds its 8 digest words and not the 24-word record.
+__device__ __forceinline__ void leaf_record(const uint32_t* __restrict__ sh, bool q0, const uint32_t (&st)[8],
+                                            uint32_t (&nd)[kNodeWords]) {
   if (q0) {
     const uint4* p4 = reinterpret_cast<const uint4*>(sh);
     uint32_t s[8];
@@ -155,6 +154,15 @@ __device__ __forceinline__ void make_leaf_node(const uint32_t* __restrict__ sh, 
     nd[14] = 0xFFFFu;
   }
   put_digest(nd, st);
+}
+
+// Leaf node of one EDS cell: ns || ns || SHA256(0x00 || ns || share), ns = share[0:29]
+// for Q0 cells and 0xFF*29 (parity namespace) otherwise.
+template <bool PF>
+__device__ __forceinline__ void make_leaf_node(const uint32_t* __restrict__ sh, bool q0, uint32_t (&nd)[kNodeWords]) {
+  uint32_t st[8];
+  leaf_hash<PF>(st, sh, q0);
+  leaf_record(sh, q0, st, nd);
 }
 
 // Namespace order: is ns(a) < ns(b)? (29-byte lexicographic compare of share prefixes)

@@ -11,7 +11,10 @@
 //   k_leaf   : one lane per EDS cell. A cell's row leaf and column leaf are the same
 //              bytes (the Q0 test of nmt_wrapper.go:138-140 is symmetric), so each
 //              leaf is hashed once: 4k^2 x 9 compressions instead of the reference's
-//              8k^2 x 9. Also checks the honest push order on Q0.
+//              8k^2 x 9. Also checks the honest push order on Q0. One square's commit.
+//   k_leaf_quad : a batch's leaves and level 1: one lane per 2x2 block of cells hashes
+//              its four leaves and the two row and two column nodes over them, so no
+//              leaf record is written.
 //   k_level  : one lane per inner node of one tree level, all 4k trees at once.
 //   k_dah    : one workgroup per square, RFC-6962 over the 4k roots.
 // Nodes live on the device as 96-byte records (90 B node + 6 zero bytes) = 24 dwords; a
@@ -65,6 +68,26 @@ __global__ __launch_bounds__(256) void k_leaf(const uint8_t* __restrict__ eds, u
 
 // ---------------------------------------------------------------- inner nodes
 
+// The root-level outputs of tree t's root o in square sq (k_level's last level, k_leaf_quad
+// at W = 2).
+__device__ __forceinline__ void put_root(const uint32_t (&o)[kNodeWords], uint32_t sq, uint32_t t, uint32_t W,
+                                         uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out,
+                                         uint8_t* __restrict__ col_out) {
+  {  // 90-byte record at a 2-byte aligned address: 45 halfword stores
+    uint8_t* r = (t < W ? row_out + ((uint64_t)sq * W + t) * kNode : col_out + ((uint64_t)sq * W + (t - W)) * kNode);
+    uint16_t* r16 = reinterpret_cast<uint16_t*>(r);
+#pragma unroll
+    for (int i = 0; i < 45; i++) r16[i] = (uint16_t)(o[i / 2] >> (16 * (i & 1)));
+  }
+  if (leafd) {
+    uint32_t st[8];
+    rfc_leaf90(o, st);
+    uint4* d = reinterpret_cast<uint4*>(leafd + ((uint64_t)sq * 2 * W + t) * 8);
+    d[0] = make_uint4(st[0], st[1], st[2], st[3]);
+    d[1] = make_uint4(st[4], st[5], st[6], st[7]);
+  }
+}
+
 // One tree level for all trees (hash_pair: nmt_device.hpp). Input addressing:
 //   FROM_LEAVES: tree t < W is row t (children leaves (t, 2j), (t, 2j+1));
 //                tree t >= W is column t-W (children (2j, c), (2j+1, c)).
@@ -95,21 +118,93 @@ __global__ __launch_bounds__(256) void k_level(const uint32_t* __restrict__ in, 
   hash_pair(in, li, ri, o);
   const uint64_t oi = (uint64_t)blockIdx.y * trees * nout + idx;
   store_node(out + oi * kNodeWords, o);
-  if (row_out) {
-    {  // 90-byte record at a 2-byte aligned address: 45 halfword stores
-      uint8_t* r = (t < W ? row_out + ((uint64_t)blockIdx.y * W + t) * kNode
-                          : col_out + ((uint64_t)blockIdx.y * W + (t - W)) * kNode);
-      uint16_t* r16 = reinterpret_cast<uint16_t*>(r);
+  if (row_out) put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
+}
+
+// ------------------------------------------------- leaves and level 1 in one lane
+
+// One lane per 2x2 block of EDS cells (rows 2bi, 2bi+1, columns 2bj, 2bj+1): the four
+// leaves (9 compressions each), the two row and the two column level-1 nodes over them
+// (3 each), written where k_level<false> reads a level of W/2 nodes: out[sq][tree][W/2],
+// row trees first. The leaf records never reach memory (W*W records written once and read
+// twice), and the leaves-to-level-1 launch goes.
+//   Order of work: leaf 00, leaf 01, row node (00,01); leaf 10, column node (00,10);
+// leaf 11, column node (01,11), row node (10,11). A leaf is kept across the hashes between
+// as its 8 digest words; its namespaces are read from the share again when a record is
+// formed (leaf_record). Leaves and nodes run in rolled loops with one leaf_hash and one
+// hash_node site: unrolled, the kernel is 32 compression bodies of straight-line code,
+// several times the instruction cache, with every wave at another place in it.
+//   A wave is an 8x8 tile of blocks (narrower squares: k wide, 64/k block rows): row and
+// column nodes both leave it as runs of 8 records, 768 bytes, per tree. The tile lies
+// wholly inside or outside Q0 for k >= 16, so the wave-uniform parity paths of leaf_hash
+// and hash_node fire as in k_leaf / k_level. The push-order check is k_leaf's, per cell.
+//   Built for three waves per SIMD: 151 VGPRs, no scratch (ORDER, no prefetch). Against
+// that, the headline step is ~2.5 % slower with the kernel held to four waves (128 VGPRs,
+// 10 dwords spilled around the node hashes), ~4 % at five (96 VGPRs, 39 spilled) and ~3 %
+// left alone (206 VGPRs, two waves): profiles/r7_leaf_quad_waves.txt.
+//   grid: x = 256 blocks, y = square. ROOTS: W = 2, the one block's level-1 nodes are the
+// four roots (out = roots [sq][4], put_root as k_level's last level).
+template <bool ORDER, bool PF, bool ROOTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad(
+    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, int32_t* __restrict__ bad_axis,
+    uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out, uint8_t* __restrict__ col_out) {
+  const uint32_t W = 2 * k, trees = 2 * W;
+  const uint32_t tw = k < 8 ? k : 8u, th = 64 / tw, tiles_x = k / tw;
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x, tile = g / 64, l = g % 64;
+  const uint32_t bi = (tile / tiles_x) * th + l / tw, bj = (tile % tiles_x) * tw + l % tw;
+  if (bi >= k) return;
+  const uint64_t sq_eds = (uint64_t)W * W * kShare;
+  const uint32_t* sh00 =
+      reinterpret_cast<const uint32_t*>(eds + blockIdx.y * sq_eds + ((uint64_t)(2 * bi) * W + 2 * bj) * kShare);
+  // leaf digests (SHA state words): dA of cell 00, then, 00 being done with, of cell 11;
+  // dB of cell 01, dC of cell 10
+  uint32_t dA[8], dB[8], dC[8];
+#pragma unroll 1
+  for (uint32_t s = 0; s < 4; s++) {  // cell s = (s >> 1, s & 1) of the block
+    const uint32_t r = 2 * bi + (s >> 1), c = 2 * bj + (s & 1);
+    const uint32_t* sh = sh00 + ((uint64_t)(s >> 1) * W + (s & 1)) * (kShare / 4);
+    const bool q0 = (r < k) && (c < k);
+    {
+      uint32_t st[8];
+      leaf_hash<PF>(st, sh, q0);
 #pragma unroll
-      for (int i = 0; i < 45; i++) r16[i] = (uint16_t)(o[i / 2] >> (16 * (i & 1)));
+      for (int i = 0; i < 8; i++) {
+        if (s == 0 || s == 3) dA[i] = st[i];
+        if (s == 1) dB[i] = st[i];
+        if (s == 2) dC[i] = st[i];
+      }
     }
-  }
-  if (leafd) {
-    uint32_t st[8];
-    rfc_leaf90(o, st);
-    uint4* d = reinterpret_cast<uint4*>(leafd + oi * 8);
-    d[0] = make_uint4(st[0], st[1], st[2], st[3]);
-    d[1] = make_uint4(st[4], st[5], st[6], st[7]);
+    // nodes this leaf completes, the leaf being their right child: s = 1: row (00,01);
+    // s = 2: column (00,10); s = 3: column (01,11), then row (10,11)
+    const uint32_t nn = s == 3 ? 2u : (s ? 1u : 0u);
+#pragma unroll 1
+    for (uint32_t n = 0; n < nn; n++) {
+      const uint32_t lc = s < 3 ? 0u : 1u + n;  // the left child's cell
+      const bool row = (s == 1) || (s == 3 && n == 1);
+      const uint32_t* shl = sh00 + ((uint64_t)(lc >> 1) * W + (lc & 1)) * (kShare / 4);
+      const bool q0l = (2 * bi + (lc >> 1) < k) && (2 * bj + (lc & 1) < k);
+      uint32_t o[kNodeWords];
+      {
+        uint32_t L[kNodeWords], R[kNodeWords], dl[8], dr[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          dl[i] = lc == 0 ? dA[i] : (lc == 1 ? dB[i] : dC[i]);
+          dr[i] = s == 1 ? dB[i] : (s == 2 ? dC[i] : dA[i]);
+        }
+        leaf_record(shl, q0l, dl, L);
+        leaf_record(sh, q0, dr, R);
+        hash_node(L, R, o);
+      }
+      const uint32_t t = row ? r : W + c, idx = row ? bj : bi;
+      store_node(out + (((uint64_t)blockIdx.y * trees + t) * k + idx) * kNodeWords, o);
+      if (ROOTS) put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
+    }
+    // after the hashes, as in k_leaf: done first, the share prefixes stay live across them
+    __builtin_amdgcn_sched_barrier(0);
+    if (ORDER && q0) {
+      if (c > 0 && ns_less(sh, sh - kShare / 4)) atomicMin(bad_axis + blockIdx.y, (int32_t)r);
+      if (r > 0 && ns_less(sh, sh - (uint64_t)W * kShare / 4)) atomicMin(bad_axis + blockIdx.y, (int32_t)(W + c));
+    }
   }
 }
 
@@ -238,19 +333,26 @@ void launch_merkle(const uint32_t* items, const uint32_t* leafd, uint32_t n, uin
                      out_src, host_out, out_bytes);
 }
 
-// Workspace: leaves [nsq][W*W] nodes | ping [nsq][2W][W/2] | pong [nsq][2W][W/4] |
-//            roots [nsq][2W] nodes | bad_axis [nsq] int32 | DAH leaf digests [nsq][2W][8]
+// Workspace: leaves [nsq][W*W] nodes (one square only) | ping [nsq][2W][W/2] |
+//            pong [nsq][2W][W/4] | roots [nsq][2W] nodes | bad_axis [nsq] int32 |
+//            DAH leaf digests [nsq][2W][8]
 struct CommitWork {
   uint32_t *leaves, *ping, *pong, *roots, *leafd;
   int32_t* bad;
   size_t size;
 };
 
+// One square is committed for its latency (a block's header, a repair's check): k_leaf
+// and k_level<true> put 4k^2 lanes on a chain of 9 + 3 compressions. k_leaf_quad has k^2
+// lanes on a chain of 48, which at k = 128 leaves three SIMDs of four without a wave. A
+// batch fills the device either way, and there the quad kernel's saved traffic counts.
+static bool quad_path(uint32_t nsq) { return nsq > 1; }
+
 static CommitWork commit_work(void* work, uint32_t k, uint32_t nsq) {
   const size_t W = 2 * (size_t)k, nb = kNodeWords * 4;
   Carver c(work);
   CommitWork w;
-  w.leaves = c.take<uint32_t>(nsq * W * W * nb);
+  w.leaves = c.take<uint32_t>(quad_path(nsq) ? 0 : nsq * W * W * nb);
   w.ping = c.take<uint32_t>(nsq * 2 * W * (W / 2 + 1) * nb);
   w.pong = c.take<uint32_t>(nsq * 2 * W * (W / 4 + 1) * nb);
   w.roots = c.take<uint32_t>(nsq * 2 * W * nb);
@@ -264,6 +366,7 @@ size_t nmt_workspace_size(uint32_t k, uint32_t nsq) { return commit_work(nullptr
 
 hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, void* work, bool order_check,
                                 uint32_t row0, uint32_t row1, bool init_bad, hipStream_t s) {
+  if (quad_path(nsq)) return hipErrorInvalidValue;  // no leaf area in that workspace
   const uint32_t W = 2 * k;
   const CommitWork w = commit_work(work, k, nsq);
   const Range r("nmt.leaf");
@@ -278,17 +381,20 @@ hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, vo
   return hipGetLastError();
 }
 
-hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
-                               int32_t* status, void* work, hipStream_t s, uint8_t* host_out, uint32_t out_bytes) {
+// The tree levels from level `nin` nodes per tree down to the roots, then the DAH. One
+// launch per level, all 4k trees of all squares at once: every lane hashes one node, no
+// idle lanes. The last level writes the root records. from_leaves: nin = W, the first
+// level reads the leaf area; otherwise nin = W / 2 in ping (k_leaf_quad's output; at W = 2
+// those are the roots and no level is left).
+static hipError_t commit_levels(const CommitWork& w, bool from_leaves, uint32_t k, uint32_t nsq, uint8_t* row_roots,
+                                uint8_t* col_roots, uint8_t* dah, int32_t* status, hipStream_t s, uint8_t* host_out,
+                                uint32_t out_bytes) {
   const uint32_t W = 2 * k;
-  const CommitWork w = commit_work(work, k, nsq);
-  // One launch per tree level, all 4k trees of all squares at once: every lane hashes
-  // one node, no idle lanes. The last level writes the root records.
   const uint32_t trees = 2 * W;
-  uint32_t nin = W;
-  const uint32_t* src = w.leaves;
-  uint32_t* dst = w.ping;
-  bool first = true;
+  uint32_t nin = from_leaves ? W : W / 2;
+  const uint32_t* src = from_leaves ? w.leaves : w.ping;
+  uint32_t* dst = from_leaves ? w.ping : w.pong;
+  bool first = from_leaves;
   roctxRangePushA("nmt.levels");
   while (nin > 1) {
     const uint32_t nout = nin / 2;
@@ -313,10 +419,49 @@ hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uin
   return hipGetLastError();
 }
 
+hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
+                               int32_t* status, void* work, hipStream_t s, uint8_t* host_out, uint32_t out_bytes) {
+  if (quad_path(nsq)) return hipErrorInvalidValue;
+  return commit_levels(commit_work(work, k, nsq), true, k, nsq, row_roots, col_roots, dah, status, s, host_out,
+                       out_bytes);
+}
+
+// Leaves and level 1 of every square in one launch (k_leaf_quad), level-1 nodes into ping.
+static hipError_t launch_commit_quads(const uint8_t* eds, uint32_t k, uint32_t nsq, const CommitWork& w,
+                                      bool order_check, uint8_t* row_roots, uint8_t* col_roots, bool want_dah,
+                                      hipStream_t s) {
+  const Range r("nmt.leaf");
+  launch_fill_i32(w.bad, nsq, INT_MAX, 256, s);
+  const uint32_t tw = k < 8 ? k : 8u, th = 64 / tw;  // a wave's tile of blocks, as in the kernel
+  const uint64_t lanes = (uint64_t)((k + th - 1) / th) * (k / tw) * 64;
+  dim3 g((uint32_t)((lanes + 255) / 256), nsq);
+  if (k == 1) {
+    uint32_t* ld = want_dah ? w.leafd : nullptr;
+    if (order_check)
+      hipLaunchKernelGGL((k_leaf_quad<true, false, true>), g, dim3(256), 0, s, eds, k, w.roots, w.bad, ld,
+                         row_roots, col_roots);
+    else
+      hipLaunchKernelGGL((k_leaf_quad<false, false, true>), g, dim3(256), 0, s, eds, k, w.roots, w.bad, ld,
+                         row_roots, col_roots);
+    return hipGetLastError();
+  }
+  dispatch_order_pf(order_check, latency_bound(lanes * nsq), [&](auto order, auto pf) {
+    hipLaunchKernelGGL((k_leaf_quad<decltype(order)::value, decltype(pf)::value, false>), g, dim3(256), 0, s, eds, k,
+                       w.ping, w.bad, nullptr, nullptr, nullptr);
+  });
+  return hipGetLastError();
+}
+
 hipError_t launch_commit(const uint8_t* eds, uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* col_roots,
                          uint8_t* dah, int32_t* status, void* work, bool order_check, hipStream_t s) {
-  hipError_t e = launch_commit_leaves(eds, k, nsq, work, order_check, 0, 2 * k, true, s);
-  if (e == hipSuccess) e = launch_commit_trees(k, nsq, row_roots, col_roots, dah, status, work, s);
+  if (!quad_path(nsq)) {
+    hipError_t e = launch_commit_leaves(eds, k, nsq, work, order_check, 0, 2 * k, true, s);
+    if (e == hipSuccess) e = launch_commit_trees(k, nsq, row_roots, col_roots, dah, status, work, s);
+    return e;
+  }
+  const CommitWork w = commit_work(work, k, nsq);
+  hipError_t e = launch_commit_quads(eds, k, nsq, w, order_check, row_roots, col_roots, dah != nullptr, s);
+  if (e == hipSuccess) e = commit_levels(w, false, k, nsq, row_roots, col_roots, dah, status, s, nullptr, 0);
   return e;
 }
 
