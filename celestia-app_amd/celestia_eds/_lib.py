@@ -41,6 +41,8 @@ EXPORTS = [
     "cel_shard_plan_last_error", "cel_shard_plan_note", "cel_shard_plan_time_exchange", "cel_shard_plan_upload", "cel_shard_plan_run", "cel_shard_plan_wait",
     "cel_extend_batch_multi", "cel_probe_sha256", "cel_probe_hbm_copy", "cel_probe_hbm_stream",
     "cel_probe_rs_transform",
+    "cel_nmt_verify_batch", "cel_dev_nmt_verify_workspace_size", "cel_dev_nmt_verify_batch",
+    "cel_dev_place_samples", "cel_repair_samples",
 ]
 
 _lib = None
@@ -131,6 +133,11 @@ def load():
             "cel_probe_hbm_copy": (i32, [P, u64, ctypes.POINTER(ctypes.c_double)]),
             "cel_probe_hbm_stream": (i32, [P, u64] + [ctypes.POINTER(ctypes.c_double)] * 3),
             "cel_probe_rs_transform": (i32, [P, u32, ctypes.POINTER(ctypes.c_double)]),
+            "cel_nmt_verify_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, u32, P, P]),
+            "cel_dev_nmt_verify_workspace_size": (sz, [u64, u64, u32]),
+            "cel_dev_nmt_verify_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, u32, P, P, P, P]),
+            "cel_dev_place_samples": (i32, [P, P, P, u32, P, P, u32, P, P, P, P, P, P, P]),
+            "cel_repair_samples": (i32, [P, u32, P, P, u32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(l, name)

@@ -14,6 +14,10 @@ v0.22.0 proof.go [dep]: leaf hashing with the namespace prefix, completeness che
 computeRoot) and go-square merkle Proof.Verify (RFC-6962). Host-side hashing is the
 reference's own choice for verifiers (a light client verifies on its CPU).
 
+A node that reconstructs squares or validates many ShareProofs checks tens of thousands of
+NMT proofs per square: VerifyInclusionBatch / VerifyShareProofs run those on the device
+(cel_nmt_verify_batch), with the host verifier above as their checker.
+
 Wire format (proto/celestia/core/v1/proof/proof.proto:8-49, gogoproto-generated
 pkg/proof/proof.pb.go): ShareProof / RowProof / NMTProof / Proof .Marshal() and
 Unmarshal(bytes), the bytes QueryTxInclusionProof / QueryShareInclusionProof return
@@ -585,3 +589,83 @@ def NewTxInclusionProof(txs, tx_index, max_square_size=128, subtree_root_thresho
     ods = square.Construct(txs, max_square_size, subtree_root_threshold)
     ns = PFB_NAMESPACE if bytes(ods[start][:NS]) == PFB_NAMESPACE else TX_NAMESPACE
     return NewShareInclusionProof(list(ods), ns, start, end)
+
+
+# ------------------------------------------------------- batched verification
+def VerifyInclusionBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
+    """NMTProof.VerifyInclusion(namespaces[i], leaves_per_proof[i], roots[i]) for every proof
+    in one device batch (cel_nmt_verify_batch): a list of bools. The device verifies the
+    app's sizes: a proof with a node that is not 90 bytes long, a leaf that is not 512, a
+    namespace that is not 29 or a root that is not 90 is False without reaching the device."""
+    n = len(proofs)
+    if not (len(namespaces) == len(leaves_per_proof) == len(roots) == n):
+        raise CelError(_lib.EINVAL, "proofs, namespaces, leaves and roots differ in number")
+    out = [False] * n
+    share = _lib.SHARE_SIZE
+    keep = [i for i in range(n)
+            if len(namespaces[i]) == NS and len(roots[i]) == NODE
+            and -(1 << 31) <= proofs[i].Start < 1 << 31 and -(1 << 31) <= proofs[i].End < 1 << 31
+            and all(len(x) == NODE for x in proofs[i].Nodes) and all(len(x) == share for x in leaves_per_proof[i])]
+    if not keep:
+        return out
+    ctx = ctx or _lib.default_context()
+    root_at, root_idx = {}, []
+    for i in keep:
+        root_idx.append(root_at.setdefault(bytes(roots[i]), len(root_at)))
+    leaf_off = np.cumsum([0] + [len(leaves_per_proof[i]) for i in keep]).astype(np.uint64)
+    node_off = np.cumsum([0] + [len(proofs[i].Nodes) for i in keep]).astype(np.uint64)
+    buf = lambda parts: np.frombuffer(b"".join(parts) or b"\0", np.uint8).copy()
+    starts = np.array([proofs[i].Start for i in keep], np.int32)
+    ends = np.array([proofs[i].End for i in keep], np.int32)
+    ns = buf(bytes(namespaces[i]) for i in keep)
+    leaves = buf(bytes(x) for i in keep for x in leaves_per_proof[i])
+    nodes = buf(bytes(x) for i in keep for x in proofs[i].Nodes)
+    rts = buf(root_at)
+    ridx = np.array(root_idx, np.uint32)
+    ok = np.zeros(len(keep), np.uint8)
+    ctx.check(ctx.lib.cel_nmt_verify_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(ns), _p(leaves),
+                                           _p(leaf_off), _p(nodes), _p(node_off), _p(rts), len(root_at), _p(ridx),
+                                           _p(ok)))
+    for i, v in zip(keep, ok):
+        out[i] = bool(v)
+    return out
+
+
+def VerifyShareProofs(share_proofs, root, ctx=None):
+    """[True where share_proofs[i].Validate(root) would not raise]. The structural checks of
+    ShareProof.Validate and the RFC-6962 row proofs (18 compressions per row) run on the
+    host; every NMT range proof of every ShareProof goes through one device batch."""
+    out = [False] * len(share_proofs)
+    proofs, nss, leaves, roots, owner = [], [], [], [], []
+    for i, sp in enumerate(share_proofs):
+        try:  # ShareProof.Validate up to its VerifyProof
+            if sp.RowProof is None or not sp.Data:
+                continue
+            if len(sp.ShareProofs) != len(sp.RowProof.RowRoots):
+                continue
+            if len(sp.Data) != sum(p.End - p.Start for p in sp.ShareProofs):
+                continue
+            if any(p.Start < 0 or p.End - p.Start <= 0 for p in sp.ShareProofs):
+                continue
+            sp.RowProof.Validate(root)
+        except CelError:
+            continue
+        if sp.NamespaceVersion > 255:
+            continue
+        ns = bytes([sp.NamespaceVersion]) + bytes(sp.NamespaceId)
+        if len(ns) != NS:  # nmt is generic in the namespace size, the device is not
+            out[i] = sp.VerifyProof()
+            continue
+        out[i] = True  # unless one of its range proofs fails
+        cursor = 0
+        for j, p in enumerate(sp.ShareProofs):
+            used = p.End - p.Start
+            proofs.append(p)
+            nss.append(ns)
+            leaves.append(sp.Data[cursor:cursor + used])
+            roots.append(sp.RowProof.RowRoots[j])
+            owner.append(i)
+            cursor += used
+    for i, v in zip(owner, VerifyInclusionBatch(proofs, nss, leaves, roots, ctx=ctx)):
+        out[i] = out[i] and v
+    return out

@@ -5,6 +5,7 @@ Mirrors the pieces of github.com/celestiaorg/rsmt2d that celestia-app uses
   LeoRSCodec: Encode / Decode / MaxChunks / Name / ValidateChunkSize
   ComputeExtendedDataSquare, ImportExtendedDataSquare, ExtendedDataSquare.{RowRoots,
   ColRoots, Row, Col, GetCell, Flattened, Width, Repair}
+  RepairFromSamples: cells with NMT inclusion proofs, verified on the device, then Repair
 All arithmetic runs in libcelestia_eds.so (HIP); this module marshals bytes.
 
 Tree constructors. rsmt2d computes each axis root through the TreeConstructorFn it
@@ -226,3 +227,52 @@ def ImportExtendedDataSquare(flattened, codec=None, tree_constructor=None, ctx=N
     w = int(round(n ** 0.5))
     cells = np.frombuffer(b"".join(flattened), np.uint8).reshape(w, w, -1).copy()
     return ExtendedDataSquare(cells, ctx=ctx, tree_constructor=tree_constructor)
+
+
+def RepairFromSamples(k, samples, row_roots, col_roots, ctx=None):
+    """Repair a 2k x 2k square from sampled cells that come with NMT inclusion proofs
+    (cel_repair_samples): samples = (row, col, axis, share, nodes) with `nodes` the
+    single-leaf nmt proof of the cell against row_roots[row] (axis Row) or col_roots[col]
+    (axis Col). Every proof is verified on the device; accepted samples fill the square,
+    which is then repaired as ExtendedDataSquare.Repair does. Returns (ExtendedDataSquare,
+    ok) with ok[i] the verdict of sample i; a share that is not 512 bytes long or a node
+    that is not 90 is False without reaching the device. Raises what Repair raises."""
+    ctx = ctx or _lib.default_context()
+    w, share, node = 2 * k, _lib.SHARE_SIZE, _lib.NMT_NODE_SIZE
+    samples = list(samples)
+    ok = [False] * len(samples)
+    keep = [i for i, s in enumerate(samples) if len(s[3]) == share and all(len(x) == node for x in s[4])
+            and 0 <= s[0] < 1 << 32 and 0 <= s[1] < 1 << 32 and 0 <= s[2] < 256]
+    buf = lambda parts: np.frombuffer(b"".join(parts) or b"\0", np.uint8).copy()
+    rows = np.array([samples[i][0] for i in keep] or [0], np.uint32)
+    cols = np.array([samples[i][1] for i in keep] or [0], np.uint32)
+    axes = np.array([samples[i][2] for i in keep] or [0], np.uint8)
+    shares = buf(bytes(samples[i][3]) for i in keep)
+    nodes = buf(bytes(x) for i in keep for x in samples[i][4])
+    node_off = np.cumsum([0] + [len(samples[i][4]) for i in keep]).astype(np.uint64)
+    rr = np.frombuffer(b"".join(row_roots), np.uint8).copy()
+    cr = np.frombuffer(b"".join(col_roots), np.uint8).copy()
+    if rr.size != w * node or cr.size != w * node:
+        raise CelError(_lib.EINVAL, f"need {w} row roots and {w} column roots of {node} bytes")
+    okd = np.zeros(max(len(keep), 1), np.uint8)
+    cells = np.zeros((w, w, share), np.uint8)
+    mask = np.zeros((w, w), np.uint8)
+    ba, bi = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    bs = np.zeros((w, share), np.uint8)
+    bp = np.zeros(w, np.uint8)
+    st = ctx.lib.cel_repair_samples(ctx.handle, k, _p(rr), _p(cr), len(keep), _p(rows), _p(cols), _p(axes),
+                                    _p(shares), _p(nodes), _p(node_off), _p(okd), _p(cells), _p(mask),
+                                    ctypes.byref(ba), ctypes.byref(bi), _p(bs), _p(bp))
+    for i, v in zip(keep, okd):
+        ok[i] = bool(v)
+    sq = ExtendedDataSquare(cells, ctx=ctx)
+    sq._mask = mask
+    if st == _lib.EBYZANTINE:
+        shares_out = [bs[j].tobytes() if bp[j] else None for j in range(w)]
+        raise ErrByzantineData(ba.value, bi.value, ctx.lib.cel_last_error(ctx.handle).decode(), shares_out)
+    if st == _lib.EUNREPAIRABLE:
+        raise ErrUnrepairableDataSquare()
+    ctx.check(st)
+    sq._row_roots = rr.reshape(w, -1).copy()
+    sq._col_roots = cr.reshape(w, -1).copy()
+    return sq, ok

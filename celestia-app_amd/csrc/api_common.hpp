@@ -95,6 +95,11 @@ cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off
                           const CommitItem* items, uint32_t nb, uint32_t threshold, uint8_t* d_out, void* d_work,
                           hipStream_t s);
 
+// cel_dev_repair's body, for a caller that holds ctx->mu (api_repair.cpp).
+cel_status dev_repair_locked(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t k, const uint8_t* row_roots,
+                             const uint8_t* col_roots, int32_t* bad_axis, int32_t* bad_index, uint8_t* byz_shares,
+                             uint8_t* byz_present);
+
 inline cel_status validate_square(cel_ctx* ctx, uint32_t k, uint32_t share_size) {
   if (share_size != kShare)
     return fail(ctx, CEL_ECHUNK, "share size must be appconsts.ShareSize (512) on the device path");

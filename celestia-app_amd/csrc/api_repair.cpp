@@ -937,6 +937,15 @@ cel_status cel_dev_repair(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t 
                           uint8_t* byz_present) {
   if (!ctx) return CEL_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);
+  return dev_repair_locked(ctx, d_eds, present, k, row_roots, col_roots, bad_axis, bad_index, byz_shares, byz_present);
+}
+
+}  // extern "C"
+
+// cel_dev_repair with ctx->mu held (also the second half of cel_repair_samples, api_verify.cpp).
+cel_status cel::abi::dev_repair_locked(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t k,
+                                       const uint8_t* row_roots, const uint8_t* col_roots, int32_t* bad_axis,
+                                       int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present) {
   if (!d_eds || !present || !row_roots || !col_roots) return fail(ctx, CEL_EINVAL, "nil argument");
   cel_status st = validate_square(ctx, k, kShare);
   if (st) return st;
@@ -954,5 +963,3 @@ cel_status cel_dev_repair(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t 
     std::memcpy(present, hm.data(), cells);
   return st;
 }
-
-}  // extern "C"

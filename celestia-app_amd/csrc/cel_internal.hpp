@@ -303,9 +303,10 @@ struct cel_ctx {
   // Grow-only page-locked host staging (the repair's axis lists).
   void* hstage = nullptr;
   size_t hstage_size = 0;
-  // Page-locked plan tables of the blob commitment calls (api_commit.cpp). The asynchronous
-  // entry returns while their upload may still be queued, so they have a buffer of their
-  // own and the next call waits for ev_plan (recorded after the upload) before refilling it.
+  // Page-locked plan tables of the blob commitment calls (api_commit.cpp) and proof tables of
+  // the NMT verifier (api_verify.cpp). The asynchronous entry returns while their upload may
+  // still be queued, so they have a buffer of their own and the next call waits for ev_plan
+  // (recorded after the upload) before refilling it.
   void* plan_stage = nullptr;
   size_t plan_stage_size = 0;
   hipEvent_t ev_plan = nullptr;

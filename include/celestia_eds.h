@@ -393,6 +393,55 @@ cel_status cel_nmt_prove_range(const uint8_t* tree_nodes, uint32_t nleaves, uint
 cel_status cel_merkle_aunts(const uint8_t* tree, uint32_t n, uint32_t index, uint8_t* aunts_out,
                             uint32_t* naunts);
 
+/* ------------------------------------------------- proof verification, samples
+ * nmt Proof.VerifyInclusion (nmt v0.22.0 proof.go [dep]) for n proofs in one device batch:
+ * the NMT range proofs of ShareProofs (pkg/proof/share_proof.go:60-82) and of sampled
+ * cells. Proof i: range [starts[i], ends[i]), namespace namespaces[29*i..], its leaves =
+ * the 512-byte shares leaf_off[i]..leaf_off[i+1] of `leaves` (without namespace prefix:
+ * the namespace hashed in front of a leaf is the proof's, whatever the share starts
+ * with), its nodes = the 90-byte nodes node_off[i]..node_off[i+1] of `nodes` (nmt order),
+ * its root = roots[90*root_idx[i]..]. ok_out[i] = 1 iff it verifies. The proofs are
+ * untrusted: start < 0, end <= start, a leaf count other than end - start, a missing
+ * node, unordered children are verdict 0, never an error of the call.
+ * CEL_EINVAL: nil argument, decreasing offsets, root_idx[i] >= nroots. n = 0 is CEL_OK. */
+cel_status cel_nmt_verify_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
+                                const uint8_t* namespaces, const uint8_t* leaves, const uint64_t* leaf_off,
+                                const uint8_t* nodes, const uint64_t* node_off, const uint8_t* roots,
+                                uint32_t nroots, const uint32_t* root_idx, uint8_t* ok_out);
+/* Same with leaves (16-byte aligned), nodes, roots and ok (n bytes) in device memory; the
+ * small per-proof arrays stay host. d_work: cel_dev_nmt_verify_workspace_size bytes for
+ * the batch's leaves (leaf_off[n] - leaf_off[0]), nodes and proofs. Asynchronous on stream
+ * (NULL = the ctx's own), in the style of cel_dev_create_commitments: the host arrays are
+ * consumed before the call returns. */
+size_t cel_dev_nmt_verify_workspace_size(uint64_t total_leaves, uint64_t total_nodes, uint32_t n);
+cel_status cel_dev_nmt_verify_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
+                                    const uint8_t* namespaces, const void* d_leaves, const uint64_t* leaf_off,
+                                    const void* d_nodes, const uint64_t* node_off, const void* d_roots,
+                                    uint32_t nroots, const uint32_t* root_idx, void* d_ok, void* d_work,
+                                    void* stream);
+/* Samples into a device EDS (d_eds: 2k*2k*512 bytes; present: host, 2k*2k). Sample i is
+ * cell (rows[i], cols[i]) with share shares[512*i..] and a single-leaf nmt proof (nodes
+ * node_off[i]..node_off[i+1]) against row_roots[rows[i]] at leaf cols[i] (axes[i] = 0) or
+ * col_roots[cols[i]] at leaf rows[i] (axes[i] = 1). The namespace follows the wrapper's
+ * rule (nmt_wrapper.go:100-107): share[0:29] for row < k and col < k, else 0xFF*29.
+ * ok_out[i] = the verdict. A coordinate >= 2k, or an axis > 1, is verdict 0. An accepted
+ * sample whose cell is not yet present is written into d_eds and present[] set. A cell
+ * already present is left as it is. Of several accepted samples for one absent cell, the
+ * lowest index is written. Nothing of a rejected sample is written. Synchronous. */
+cel_status cel_dev_place_samples(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t k,
+                                 const uint8_t* row_roots, const uint8_t* col_roots, uint32_t n,
+                                 const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                                 const uint8_t* shares, const uint8_t* nodes, const uint64_t* node_off,
+                                 uint8_t* ok_out);
+/* The samples placed into a zeroed device square as above, then the repair of
+ * cel_dev_repair. eds_out: 2k*2k*512. present_out: 2k*2k. The status and the byzantine
+ * outputs are those of cel_repair. */
+cel_status cel_repair_samples(cel_ctx* ctx, uint32_t k, const uint8_t* row_roots, const uint8_t* col_roots,
+                              uint32_t n, const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                              const uint8_t* shares, const uint8_t* nodes, const uint64_t* node_off,
+                              uint8_t* ok_out, uint8_t* eds_out, uint8_t* present_out, int32_t* bad_axis,
+                              int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present);
+
 /* Blob share commitments from an EDS (pkg/inclusion).
  * cel_commitment_paths: calculateCommitmentPaths (paths.go:16-47) for a blob of
  * blob_share_len shares placed at the first aligned index >= start of a square of
