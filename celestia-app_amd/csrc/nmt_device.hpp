@@ -2,7 +2,8 @@
 // commit), nmt_slab.hip (the row-sharded mode), nmt_trees.hip (single trees, axes roots,
 // exported trees) and blob_commit.hip (blob share commitments): 96-byte node records, the
 // leaf hash of a 512-byte share, the namespace compares, HashNode with IgnoreMaxNamespace,
-// the inner-node step of a tree level (hash_pair), and the RFC-6962 leaf / inner hashes.
+// the inner-node step of a tree level (hash_pair), the digest-only hash of a node outside Q0
+// (hash_parity_node), and the RFC-6962 leaf / inner hashes.
 // One message per lane.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -263,6 +264,94 @@ __device__ __forceinline__ void hash_pair(const uint32_t* in, uint64_t li, uint6
   load_node(in + li * kNodeWords, L);
   load_node(in + ri * kNodeWords, R);
   hash_node(L, R, o);
+}
+
+// ------------------------------------------- parity nodes, kept as their digests
+
+// A node whose subtree lies outside Q0 has min = max = 0xFF*29, and so have both its
+// children: the batch commit (nmt_kernels.hip) knows such a node from its position and
+// keeps only its digest, the 8 big-endian SHA state words. Its message is
+// 0x01 || 0xFF*58 || dl || 0xFF*58 || dr: the 48 words below with the digest bytes zero
+// (tests/test_gpu_parity_records.py restates the layout). Digest bytes fall into 18 of them:
+// 14, 15 (block 0), 16..22 (block 1), 37..45 (block 2).
+constexpr uint32_t kParNodeWords[48] = {
+    0x01FFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu,
+    0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFF00u, 0x00000000u,
+    0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x000000FFu, 0xFFFFFFFFu,
+    0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu,
+    0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFF000000u, 0x00000000u, 0x00000000u,
+    0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000000u, 0x00800000u, 0x00000000u, 181u * 8u};
+
+// out = SHA256(0x01 || 0xFF*58 || dl || 0xFF*58 || dr), digests as state words. Block 0
+// starts at round 14 from kNodeParMid; each of the 18 digest-carrying words is one alignbit
+// of two adjacent state words (or one shift and or); the other 30 are literals, which fold
+// into the schedule of rounds 16..31 (sha256_rounds_folded). No records, no namespace tests.
+// COMPACT: rounds 32..63 of each block rolled (k_leaf_quad, whose code must stay inside the
+// instruction cache); otherwise unrolled (the level kernel).
+template <bool COMPACT>
+__device__ __forceinline__ void hash_parity_node(const uint32_t (&dl)[8], const uint32_t (&dr)[8],
+                                                 uint32_t (&out)[8]) {
+  constexpr int kEnd = COMPACT ? 32 : 64;
+  uint32_t st[8], w[16];
+  sha256_init(st);
+  auto finish = [&](ShaRegs& r) {
+    if (COMPACT) sha256_rounds_tail(r, w);
+    sha256_add(st, r);
+  };
+  {
+#pragma unroll
+    for (int i = 0; i < 14; i++) w[i] = kParNodeWords[i];
+    w[14] = kParNodeWords[14] | (dl[0] >> 24);
+    w[15] = __builtin_amdgcn_alignbit(dl[0], dl[1], 24);
+    ShaRegs r = mid_regs(kNodeParMid);
+    sha256_rounds_folded<14, kEnd>(r, w);
+    finish(r);
+  }
+  {
+#pragma unroll
+    for (int i = 0; i < 6; i++) w[i] = __builtin_amdgcn_alignbit(dl[i + 1], dl[i + 2], 24);
+    w[6] = kParNodeWords[22] | (dl[7] << 8);
+#pragma unroll
+    for (int i = 7; i < 16; i++) w[i] = kParNodeWords[16 + i];
+    ShaRegs r{st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+    sha256_rounds_folded<0, kEnd>(r, w);
+    finish(r);
+  }
+  {
+#pragma unroll
+    for (int i = 0; i < 5; i++) w[i] = kParNodeWords[32 + i];
+    w[5] = kParNodeWords[37] | (dr[0] >> 8);
+#pragma unroll
+    for (int i = 6; i < 13; i++) w[i] = __builtin_amdgcn_alignbit(dr[i - 6], dr[i - 5], 8);
+    w[13] = kParNodeWords[45] | (dr[7] << 24);
+    w[14] = kParNodeWords[46];
+    w[15] = kParNodeWords[47];
+    ShaRegs r{st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+    sha256_rounds_folded<0, kEnd>(r, w);
+    finish(r);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = st[i];
+}
+
+// The 96-byte record of a parity node from its digest: 0xFF*58 || digest bytes.
+__device__ __forceinline__ void parity_record(const uint32_t (&d)[8], uint32_t (&nd)[kNodeWords]) {
+#pragma unroll
+  for (int i = 0; i < 14; i++) nd[i] = 0xFFFFFFFFu;
+  nd[14] = 0xFFFFu;
+  put_digest(nd, d);
+}
+
+__device__ __forceinline__ void load_digest(const uint32_t* p, uint32_t (&d)[8]) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1];
+  d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+}
+
+__device__ __forceinline__ void store_digest(uint32_t* p, const uint32_t (&d)[8]) {
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(d[0], d[1], d[2], d[3]);
+  q[1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
 // ------------------------------------------------------------------ RFC-6962

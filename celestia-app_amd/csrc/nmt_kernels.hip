@@ -16,6 +16,8 @@
 //              its four leaves and the two row and two column nodes over them, so no
 //              leaf record is written.
 //   k_level  : one lane per inner node of one tree level, all 4k trees at once.
+//   k_level_split : a batch's levels above level 1: the nodes outside Q0 as 32-byte digests
+//              under a hash with their constant words folded, the Q0 nodes as records.
 //   k_dah    : one workgroup per square, RFC-6962 over the 4k roots.
 // Nodes live on the device as 96-byte records (90 B node + 6 zero bytes) = 24 dwords; a
 // slab's row-subtree records carry a mark in dword 23 (k_slab_status).
@@ -121,6 +123,80 @@ __global__ __launch_bounds__(256) void k_level(const uint32_t* __restrict__ in, 
   if (row_out) put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
 }
 
+// ------------------------------------------------------- a batch's split levels
+
+// A batch keeps every level in two classes, told apart by position alone. A node is a
+// parity node if its subtree lies outside Q0: every node of row trees k..2k-1 and column
+// trees k..2k-1, and the upper half of every level of the mixed trees (rows and columns
+// 0..k-1). Its namespaces are 0xFF*29 whatever the shares hold, so it is kept as its
+// digest (8 big-endian state words) and hashed by hash_parity_node. The lower half of a
+// mixed tree's level are Q0 nodes: 96-byte records through hash_node, also where a Q0
+// subtree's namespaces happen to be 0xFF*29. A level of n nodes per tree, per square:
+//   Q records [2k mixed trees][n/2]            mixed tree m: row m, or column m - k
+//   P digests [2k mixed trees][n/2] | [2k parity trees][n]
+//                                              parity tree p: row k + p, or column p
+// Both are plain pair reductions: node i of the next level is the hash of nodes 2i, 2i+1 of
+// this one in either array, so a level's lanes need no tree arithmetic, and a wave is of
+// one class. At n = 2 the next level is the roots: mixed tree m's is HashNode(Q[m], P[m])
+// (the join), parity tree p's the hash of P[2k + 2p], P[2k + 2p + 1].
+__host__ __device__ constexpr uint32_t q_nodes(uint32_t k, uint32_t n) { return k * n; }
+__host__ __device__ constexpr uint32_t p_nodes(uint32_t k, uint32_t n) { return 3 * k * n; }
+// node i of tree t (rows 0..2k-1, then columns) in a level of n nodes per tree
+__device__ __forceinline__ uint32_t q_node(uint32_t k, uint32_t n, uint32_t t, uint32_t i) {
+  return (t < k ? t : t - k) * (n / 2) + i;
+}
+__device__ __forceinline__ uint32_t p_node(uint32_t k, uint32_t n, uint32_t t, uint32_t i) {
+  const uint32_t W = 2 * k, a = t < W ? t : t - W;
+  if (a < k) return (t < W ? a : k + a) * (n / 2) + (i - n / 2);
+  return k * n + (t < W ? a - k : a) * n + i;
+}
+
+// One split level of a batch: nq Q0 nodes and np parity nodes per square out of twice as
+// many. grid: x = bq blocks of Q0 lanes, then the parity lanes' blocks; y = square.
+// ROOT: the last level (n = 2). The Q0 lanes are the 2k joins: the parity half's digest
+// becomes a record in registers and hash_node decides the max namespace as everywhere;
+// the parity lanes hash the 2k all-parity roots. Both write their root as k_level does.
+template <bool ROOT>
+__global__ __launch_bounds__(256) void k_level_split(const uint32_t* __restrict__ qin, uint32_t* __restrict__ qout,
+                                                     const uint32_t* __restrict__ pin, uint32_t* __restrict__ pout,
+                                                     uint32_t nq, uint32_t np, uint32_t bq, uint32_t k,
+                                                     uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out,
+                                                     uint8_t* __restrict__ col_out) {
+  const uint32_t sq = blockIdx.y, W = 2 * k;
+  if (blockIdx.x < bq) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nq) return;
+    uint32_t o[kNodeWords];
+    if (ROOT) {
+      uint32_t L[kNodeWords], R[kNodeWords], d[8];
+      load_node(qin + ((uint64_t)sq * nq + i) * kNodeWords, L);
+      load_digest(pin + ((uint64_t)sq * 3 * np + i) * 8, d);
+      parity_record(d, R);
+      hash_node(L, R, o);
+      put_root(o, sq, i < k ? i : W + (i - k), W, leafd, row_out, col_out);
+    } else {
+      hash_pair(qin + (uint64_t)sq * 2 * nq * kNodeWords, 2 * i, 2 * i + 1, o);
+      store_node(qout + ((uint64_t)sq * nq + i) * kNodeWords, o);
+    }
+  } else {
+    const uint32_t i = (blockIdx.x - bq) * 256u + threadIdx.x;
+    if (i >= np) return;
+    // ROOT: the square's digests are [2k of the joins][2k pairs]
+    const uint32_t* in = pin + (ROOT ? (uint64_t)sq * 3 * np + np : (uint64_t)sq * 2 * np) * 8;
+    uint32_t dl[8], dr[8], d[8];
+    load_digest(in + (uint64_t)i * 16, dl);
+    load_digest(in + (uint64_t)i * 16 + 8, dr);
+    hash_parity_node<false>(dl, dr, d);
+    if (ROOT) {
+      uint32_t o[kNodeWords];
+      parity_record(d, o);
+      put_root(o, sq, i < k ? k + i : W + i, W, leafd, row_out, col_out);
+    } else {
+      store_digest(pout + ((uint64_t)sq * np + i) * 8, d);
+    }
+  }
+}
+
 // ------------------------------------------------- leaves and level 1 in one lane
 
 // One lane per 2x2 block of EDS cells (rows 2bi, 2bi+1, columns 2bj, 2bj+1): the four
@@ -138,16 +214,21 @@ __global__ __launch_bounds__(256) void k_level(const uint32_t* __restrict__ in, 
 // column nodes both leave it as runs of 8 records, 768 bytes, per tree. The tile lies
 // wholly inside or outside Q0 for k >= 16, so the wave-uniform parity paths of leaf_hash
 // and hash_node fire as in k_leaf / k_level. The push-order check is k_leaf's, per cell.
-//   Built for three waves per SIMD: 151 VGPRs, no scratch (ORDER, no prefetch). Against
+//   Built for three waves per SIMD: 133 VGPRs, no scratch (ORDER, no prefetch; 151 before
+// the parity nodes had a hash of their own, measured as follows). Against
 // that, the headline step is ~2.5 % slower with the kernel held to four waves (128 VGPRs,
 // 10 dwords spilled around the node hashes), ~4 % at five (96 VGPRs, 39 spilled) and ~3 %
 // left alone (206 VGPRs, two waves): profiles/r7_leaf_quad_waves.txt.
+//   A level-1 node outside Q0 (its left leaf is; the tile's lanes all are for k >= 16) is
+// hashed by hash_parity_node from the two leaf digests and leaves as a digest into pout;
+// a Q0 node goes through hash_node and leaves as a record into out (split levels, above).
 //   grid: x = 256 blocks, y = square. ROOTS: W = 2, the one block's level-1 nodes are the
-// four roots (out = roots [sq][4], put_root as k_level's last level).
+// four roots, all through hash_node (out = roots [sq][4], put_root as k_level's last level).
 template <bool ORDER, bool PF, bool ROOTS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad(
-    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, int32_t* __restrict__ bad_axis,
-    uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out, uint8_t* __restrict__ col_out) {
+    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, uint32_t* __restrict__ pout,
+    int32_t* __restrict__ bad_axis, uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out,
+    uint8_t* __restrict__ col_out) {
   const uint32_t W = 2 * k, trees = 2 * W;
   const uint32_t tw = k < 8 ? k : 8u, th = 64 / tw, tiles_x = k / tw;
   const uint32_t g = blockIdx.x * 256u + threadIdx.x, tile = g / 64, l = g % 64;
@@ -183,21 +264,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       const bool row = (s == 1) || (s == 3 && n == 1);
       const uint32_t* shl = sh00 + ((uint64_t)(lc >> 1) * W + (lc & 1)) * (kShare / 4);
       const bool q0l = (2 * bi + (lc >> 1) < k) && (2 * bj + (lc & 1) < k);
-      uint32_t o[kNodeWords];
-      {
-        uint32_t L[kNodeWords], R[kNodeWords], dl[8], dr[8];
+      const uint32_t t = row ? r : W + c, idx = row ? bj : bi;  // the node's tree and index in level 1
+      auto children = [&](uint32_t (&dl)[8], uint32_t (&dr)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
           dl[i] = lc == 0 ? dA[i] : (lc == 1 ? dB[i] : dC[i]);
           dr[i] = s == 1 ? dB[i] : (s == 2 ? dC[i] : dA[i]);
         }
-        leaf_record(shl, q0l, dl, L);
-        leaf_record(sh, q0, dr, R);
-        hash_node(L, R, o);
+      };
+      if (ROOTS || q0l) {  // k is even: the right child of a Q0 left child is in Q0 too
+        uint32_t o[kNodeWords];
+        {
+          uint32_t L[kNodeWords], R[kNodeWords], dl[8], dr[8];
+          children(dl, dr);
+          leaf_record(shl, q0l, dl, L);
+          leaf_record(sh, q0, dr, R);
+          hash_node(L, R, o);
+        }
+        if (ROOTS) {
+          store_node(out + (((uint64_t)blockIdx.y * trees + t) * k + idx) * kNodeWords, o);
+          put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
+        } else {
+          store_node(out + ((uint64_t)blockIdx.y * q_nodes(k, k) + q_node(k, k, t, idx)) * kNodeWords, o);
+        }
+      } else {
+        uint32_t dl[8], dr[8], o[8];
+        children(dl, dr);
+        hash_parity_node<true>(dl, dr, o);
+        store_digest(pout + ((uint64_t)blockIdx.y * p_nodes(k, k) + p_node(k, k, t, idx)) * 8, o);
       }
-      const uint32_t t = row ? r : W + c, idx = row ? bj : bi;
-      store_node(out + (((uint64_t)blockIdx.y * trees + t) * k + idx) * kNodeWords, o);
-      if (ROOTS) put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
     }
     // after the hashes, as in k_leaf: done first, the share prefixes stay live across them
     __builtin_amdgcn_sched_barrier(0);
@@ -336,8 +431,13 @@ void launch_merkle(const uint32_t* items, const uint32_t* leafd, uint32_t n, uin
 // Workspace: leaves [nsq][W*W] nodes (one square only) | ping [nsq][2W][W/2] |
 //            pong [nsq][2W][W/4] | roots [nsq][2W] nodes | bad_axis [nsq] int32 |
 //            DAH leaf digests [nsq][2W][8]
+// A batch's split levels live inside ping and pong: level 1's Q records and P digests
+// (q[0], p[0]) in ping, level 2's in pong, and so on in turn. Level 1 takes
+// nsq * k^2 * (96 + 3 * 32) bytes and up to 255 of alignment, half of ping's
+// nsq * (k^2 + k) * 384; level 2 half of that against half of ping's size in pong.
 struct CommitWork {
   uint32_t *leaves, *ping, *pong, *roots, *leafd;
+  uint32_t *q[2], *p[2];
   int32_t* bad;
   size_t size;
 };
@@ -359,6 +459,11 @@ static CommitWork commit_work(void* work, uint32_t k, uint32_t nsq) {
   w.bad = c.take<int32_t>((size_t)nsq * 4 + 4);
   w.leafd = c.take<uint32_t>(nsq * 2 * W * 32);
   w.size = c.size();
+  for (uint32_t i = 0; i < 2; i++) {  // level 1 + i: k >> i nodes per tree
+    Carver a(i ? w.pong : w.ping);
+    w.q[i] = a.take<uint32_t>((size_t)nsq * q_nodes(k, k >> i) * nb);
+    w.p[i] = a.take<uint32_t>((size_t)nsq * p_nodes(k, k >> i) * 32);
+  }
   return w;
 }
 
@@ -381,20 +486,28 @@ hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, vo
   return hipGetLastError();
 }
 
-// The tree levels from level `nin` nodes per tree down to the roots, then the DAH. One
-// launch per level, all 4k trees of all squares at once: every lane hashes one node, no
-// idle lanes. The last level writes the root records. from_leaves: nin = W, the first
-// level reads the leaf area; otherwise nin = W / 2 in ping (k_leaf_quad's output; at W = 2
-// those are the roots and no level is left).
-static hipError_t commit_levels(const CommitWork& w, bool from_leaves, uint32_t k, uint32_t nsq, uint8_t* row_roots,
+// The DAH over the roots' leaf digests (written by the root level), and the status.
+static hipError_t commit_dah(const CommitWork& w, uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* dah,
+                             int32_t* status, hipStream_t s, uint8_t* host_out, uint32_t out_bytes) {
+  const Range r("dah");
+  if (dah)
+    launch_merkle(w.roots, w.leafd, 4 * k, nsq, dah, w.bad, status, s, host_out ? row_roots : nullptr, host_out,
+                  out_bytes);
+  return hipGetLastError();
+}
+
+// One square's tree levels from the leaf area down to the roots, then the DAH. One launch
+// per level, all 4k trees at once: every lane hashes one node, no idle lanes. The last
+// level writes the root records, packed into row_roots / col_roots.
+static hipError_t commit_levels(const CommitWork& w, uint32_t k, uint32_t nsq, uint8_t* row_roots,
                                 uint8_t* col_roots, uint8_t* dah, int32_t* status, hipStream_t s, uint8_t* host_out,
                                 uint32_t out_bytes) {
   const uint32_t W = 2 * k;
   const uint32_t trees = 2 * W;
-  uint32_t nin = from_leaves ? W : W / 2;
-  const uint32_t* src = from_leaves ? w.leaves : w.ping;
-  uint32_t* dst = from_leaves ? w.ping : w.pong;
-  bool first = from_leaves;
+  uint32_t nin = W;
+  const uint32_t* src = w.leaves;
+  uint32_t* dst = w.ping;
+  bool first = true;
   roctxRangePushA("nmt.levels");
   while (nin > 1) {
     const uint32_t nout = nin / 2;
@@ -411,22 +524,17 @@ static hipError_t commit_levels(const CommitWork& w, bool from_leaves, uint32_t 
     nin = nout;
   }
   roctxRangePop();
-  // roots already packed into row_roots / col_roots by the root level
-  const Range r("dah");
-  if (dah)
-    launch_merkle(w.roots, w.leafd, trees, nsq, dah, w.bad, status, s, host_out ? row_roots : nullptr, host_out,
-                  out_bytes);
-  return hipGetLastError();
+  return commit_dah(w, k, nsq, row_roots, dah, status, s, host_out, out_bytes);
 }
 
 hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
                                int32_t* status, void* work, hipStream_t s, uint8_t* host_out, uint32_t out_bytes) {
   if (quad_path(nsq)) return hipErrorInvalidValue;
-  return commit_levels(commit_work(work, k, nsq), true, k, nsq, row_roots, col_roots, dah, status, s, host_out,
-                       out_bytes);
+  return commit_levels(commit_work(work, k, nsq), k, nsq, row_roots, col_roots, dah, status, s, host_out, out_bytes);
 }
 
-// Leaves and level 1 of every square in one launch (k_leaf_quad), level-1 nodes into ping.
+// Leaves and level 1 of every square in one launch (k_leaf_quad): level 1's Q records and
+// P digests into q[0] / p[0]; at k = 1 the roots.
 static hipError_t launch_commit_quads(const uint8_t* eds, uint32_t k, uint32_t nsq, const CommitWork& w,
                                       bool order_check, uint8_t* row_roots, uint8_t* col_roots, bool want_dah,
                                       hipStream_t s) {
@@ -438,17 +546,35 @@ static hipError_t launch_commit_quads(const uint8_t* eds, uint32_t k, uint32_t n
   if (k == 1) {
     uint32_t* ld = want_dah ? w.leafd : nullptr;
     if (order_check)
-      hipLaunchKernelGGL((k_leaf_quad<true, false, true>), g, dim3(256), 0, s, eds, k, w.roots, w.bad, ld,
+      hipLaunchKernelGGL((k_leaf_quad<true, false, true>), g, dim3(256), 0, s, eds, k, w.roots, nullptr, w.bad, ld,
                          row_roots, col_roots);
     else
-      hipLaunchKernelGGL((k_leaf_quad<false, false, true>), g, dim3(256), 0, s, eds, k, w.roots, w.bad, ld,
+      hipLaunchKernelGGL((k_leaf_quad<false, false, true>), g, dim3(256), 0, s, eds, k, w.roots, nullptr, w.bad, ld,
                          row_roots, col_roots);
     return hipGetLastError();
   }
   dispatch_order_pf(order_check, latency_bound(lanes * nsq), [&](auto order, auto pf) {
     hipLaunchKernelGGL((k_leaf_quad<decltype(order)::value, decltype(pf)::value, false>), g, dim3(256), 0, s, eds, k,
-                       w.ping, w.bad, nullptr, nullptr, nullptr);
+                       w.q[0], w.p[0], w.bad, nullptr, nullptr, nullptr);
   });
+  return hipGetLastError();
+}
+
+// A batch's split levels from level 1 (k nodes per tree in q[0] / p[0]; k >= 2) down to the
+// roots: one launch per level with the Q0 lanes and the parity lanes in block ranges of
+// their own, the last one the joins and the all-parity roots.
+static hipError_t commit_levels_split(const CommitWork& w, uint32_t k, uint32_t nsq, uint8_t* row_roots,
+                                      uint8_t* col_roots, bool want_dah, hipStream_t s) {
+  const Range r("nmt.levels");
+  uint32_t at = 0;
+  for (uint32_t n = k; n > 2; n /= 2, at ^= 1) {
+    const uint32_t nq = q_nodes(k, n / 2), np = p_nodes(k, n / 2), bq = (nq + 255) / 256;
+    hipLaunchKernelGGL(k_level_split<false>, dim3(bq + (np + 255) / 256, nsq), dim3(256), 0, s, w.q[at], w.q[at ^ 1],
+                       w.p[at], w.p[at ^ 1], nq, np, bq, k, nullptr, nullptr, nullptr);
+  }
+  const uint32_t nr = 2 * k, bq = (nr + 255) / 256;  // 2k joins, 2k all-parity roots
+  hipLaunchKernelGGL(k_level_split<true>, dim3(2 * bq, nsq), dim3(256), 0, s, w.q[at], nullptr, w.p[at], nullptr, nr,
+                     nr, bq, k, want_dah ? w.leafd : nullptr, row_roots, col_roots);
   return hipGetLastError();
 }
 
@@ -461,7 +587,8 @@ hipError_t launch_commit(const uint8_t* eds, uint32_t k, uint32_t nsq, uint8_t* 
   }
   const CommitWork w = commit_work(work, k, nsq);
   hipError_t e = launch_commit_quads(eds, k, nsq, w, order_check, row_roots, col_roots, dah != nullptr, s);
-  if (e == hipSuccess) e = commit_levels(w, false, k, nsq, row_roots, col_roots, dah, status, s, nullptr, 0);
+  if (e == hipSuccess && k > 1) e = commit_levels_split(w, k, nsq, row_roots, col_roots, dah != nullptr, s);
+  if (e == hipSuccess) e = commit_dah(w, k, nsq, row_roots, dah, status, s, nullptr, 0);
   return e;
 }
 

@@ -20,6 +20,19 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 __device__ __forceinline__ uint32_t maj3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8);
 }
+// The same two with FOLD: plain operators where all three inputs are compile-time constants
+// (the builtin is not folded), for sha256_rounds_folded.
+template <bool FOLD>
+__device__ __forceinline__ uint32_t xor3f(uint32_t a, uint32_t b, uint32_t c) {
+  if (FOLD && __builtin_constant_p(a) && __builtin_constant_p(b) && __builtin_constant_p(c)) return a ^ b ^ c;
+  return xor3(a, b, c);
+}
+template <bool FOLD>
+__device__ __forceinline__ uint32_t maj3f(uint32_t a, uint32_t b, uint32_t c) {
+  if (FOLD && __builtin_constant_p(a) && __builtin_constant_p(b) && __builtin_constant_p(c))
+    return (a & b) | (a & c) | (b & c);
+  return maj3(a, b, c);
+}
 
 // byte swap of a dword via one v_perm_b32
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_amdgcn_perm(0u, x, 0x00010203u); }
@@ -46,12 +59,13 @@ struct ShaRegs {
   uint32_t a, b, c, d, e, f, g, h;
 };
 
+template <bool FOLD = false>
 __device__ __forceinline__ void sha_round(ShaRegs& r, uint32_t kw) {
-  const uint32_t S1 = xor3(rotr32(r.e, 6), rotr32(r.e, 11), rotr32(r.e, 25));
+  const uint32_t S1 = xor3f<FOLD>(rotr32(r.e, 6), rotr32(r.e, 11), rotr32(r.e, 25));
   const uint32_t ch = (r.e & r.f) | (~r.e & r.g);  // v_bfi_b32 / v_bitop3
   const uint32_t t1 = r.h + S1 + ch + kw;
-  const uint32_t S0 = xor3(rotr32(r.a, 2), rotr32(r.a, 13), rotr32(r.a, 22));
-  const uint32_t t2 = S0 + maj3(r.a, r.b, r.c);
+  const uint32_t S0 = xor3f<FOLD>(rotr32(r.a, 2), rotr32(r.a, 13), rotr32(r.a, 22));
+  const uint32_t t2 = S0 + maj3f<FOLD>(r.a, r.b, r.c);
   r.h = r.g; r.g = r.f; r.f = r.e; r.e = r.d + t1; r.d = r.c; r.c = r.b; r.b = r.a; r.a = t1 + t2;
 }
 
@@ -106,6 +120,56 @@ __device__ __forceinline__ void sha256_compress_unrolled(uint32_t (&st)[8], uint
   }
   st[0] += r.a; st[1] += r.b; st[2] += r.c; st[3] += r.d;
   st[4] += r.e; st[5] += r.f; st[6] += r.g; st[7] += r.h;
+}
+
+// Rounds [START, END) of a compression unrolled, for blocks that are mostly literals at
+// batch occupancy (hash_parity_node): up to round 31 the schedule still reads words of the
+// block itself, and the literals' sigma terms and sums fold (xor3f / maj3f: the builtin
+// alone is not folded). From round 32 on every term is a run-time word. END = 64 unrolls
+// those too, with K as literals and no loop; END = 32 leaves them to sha256_rounds_tail,
+// the rolled body of sha256_compress_from, where code size counts: unrolled throughout,
+// three blocks are 29 KB of code, and k_leaf_quad with them 70 KB, past the 64 KB
+// instruction cache.
+//   Left alone, the compiler computes the unrolled schedule words ahead of all rounds (the
+// VGPR note above; 137 VGPRs for the hash alone). So each run-time word passes through an
+// empty asm together with a working variable of its round: it cannot be computed before
+// the round two before it, and the window stays 16 words. The asm emits no instruction.
+template <int START, int END>
+__device__ __forceinline__ void sha256_rounds_folded(ShaRegs& r, uint32_t (&w)[16]) {
+#pragma unroll
+  for (int i = START; i < 16; i++) sha_round<true>(r, w[i] + kSha256K[i]);
+#pragma unroll
+  for (int i = 16; i < END; i++) {
+    const int j = i & 15;
+    const uint32_t w15 = w[(j + 1) & 15], w2 = w[(j + 14) & 15];
+    const uint32_t s0 = xor3f<true>(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+    const uint32_t s1 = xor3f<true>(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+    uint32_t wi = w[j] + s0 + w[(j + 9) & 15] + s1;
+    if (!__builtin_constant_p(wi)) asm volatile("" : "+v"(wi), "+v"(r.e));
+    w[j] = wi;
+    sha_round<true>(r, wi + kSha256K[i]);
+  }
+}
+
+__device__ __forceinline__ void sha256_add(uint32_t (&st)[8], const ShaRegs& r) {
+  st[0] += r.a; st[1] += r.b; st[2] += r.c; st[3] += r.d;
+  st[4] += r.e; st[5] += r.f; st[6] += r.g; st[7] += r.h;
+}
+
+// Rounds [32, 64) after sha256_rounds_folded<START, 32>, rolled.
+__device__ __forceinline__ void sha256_rounds_tail(ShaRegs& r, uint32_t (&w)[16]) {
+#pragma unroll 1
+  for (int base = 32; base < 64; base += 16) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const uint32_t w15 = w[(j + 1) & 15], w2 = w[(j + 14) & 15];
+      const uint32_t s0 = xor3(rotr32(w15, 7), rotr32(w15, 18), w15 >> 3);
+      const uint32_t s1 = xor3(rotr32(w2, 17), rotr32(w2, 19), w2 >> 10);
+      const uint32_t wi = w[j] + s0 + w[(j + 9) & 15] + s1;
+      w[j] = wi;
+      sha_round(r, wi + kSha256K[base + j]);
+    }
+  }
 }
 
 // Compile-time SHA-256: working variables after the first n rounds of a first block
