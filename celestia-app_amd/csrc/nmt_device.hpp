@@ -58,8 +58,15 @@ constexpr ShaMid kLeafParMid = sha_midstate(kLeafParPrefix, 7);
 // covers a block's load latency, which the plain form exposes nine times per leaf; at
 // batch occupancy other waves cover it and the 17 extra VGPRs cost 1.5-3 %
 // (profiles/r2_nmt_leaf_prefetch_ab.txt), so the batch keeps PF = false.
-template <bool PF>
+// What a call site knows about its cells at compile time. kAny: the class is q0, per lane,
+// with the wave-uniform shortcut below. kQ0 / kParity: every lane of every wave is of that
+// class (the batch's kernels per tile class, nmt_kernels.hip); q0 is not read, and block 0
+// has one form.
+enum class Cells { kAny, kQ0, kParity };
+
+template <bool PF, Cells C = Cells::kAny>
 __device__ __forceinline__ void leaf_hash(uint32_t (&st)[8], const uint32_t* __restrict__ sh, bool q0) {
+  if (C != Cells::kAny) q0 = C == Cells::kQ0;
   sha256_init(st);
   uint32_t w[16];
   uint32_t nx[17];  // PF: the next block's share dwords
@@ -82,7 +89,8 @@ __device__ __forceinline__ void leaf_hash(uint32_t (&st)[8], const uint32_t* __r
     if (PF) load17(1);
 #pragma unroll
     for (int i = 8; i < 16; i++) w[i] = perm(s[i - 8], s[i - 7], 0x06070001u);
-    if (__all(!q0)) {  // wave-uniform parity cells: rounds 0..6 are one constant
+    // wave-uniform parity cells: rounds 0..6 are one constant
+    if (C == Cells::kParity || (C == Cells::kAny && __all(!q0))) {
 #pragma unroll
       for (int i = 0; i < 7; i++) w[i] = kLeafParPrefix[i];
       w[7] = 0xFFFF0000u | perm(0u, s[0], 0x0C0C0001u);
@@ -216,16 +224,20 @@ __device__ __forceinline__ uint32_t node_word(const uint32_t (&L)[kNodeWords], c
   return 0u;
 }
 
+// PAR_START = false leaves the wave-uniform start out: the same bytes from one form of
+// block 0, for a kernel whose nodes all lie inside Q0 (a parity left child there is a Q0
+// share that carries 0xFF*29 itself) and whose code size counts.
+template <bool PAR_START = true>
 __device__ __forceinline__ void hash_node(const uint32_t (&L)[kNodeWords], const uint32_t (&R)[kNodeWords],
                                           uint32_t (&out)[kNodeWords]) {
   uint32_t st[8];
   sha256_init(st);
-  bool lpar = (L[14] & 0xFFFFu) == 0xFFFFu;
+  bool lpar = PAR_START && (L[14] & 0xFFFFu) == 0xFFFFu;
 #pragma unroll
   for (int i = 0; i < 14; i++) lpar = lpar && (L[i] == 0xFFFFFFFFu);
   {
     uint32_t w[16];
-    if (__all(lpar)) {  // wave-uniform: the whole wave starts block 0 at round 14
+    if (PAR_START && __all(lpar)) {  // wave-uniform: the whole wave starts block 0 at round 14
 #pragma unroll
       for (int wi = 0; wi < 14; wi++) w[wi] = kNodeParPrefix[wi];
       w[14] = node_word(L, R, 14);
@@ -286,8 +298,9 @@ constexpr uint32_t kParNodeWords[48] = {
 // starts at round 14 from kNodeParMid; each of the 18 digest-carrying words is one alignbit
 // of two adjacent state words (or one shift and or); the other 30 are literals, which fold
 // into the schedule of rounds 16..31 (sha256_rounds_folded). No records, no namespace tests.
-// COMPACT: rounds 32..63 of each block rolled (k_leaf_quad, whose code must stay inside the
-// instruction cache); otherwise unrolled (the level kernel).
+// COMPACT: rounds 32..63 of each block rolled (the mixed k_leaf_quad, which carries hash_node
+// beside it and must stay inside the instruction cache); otherwise unrolled (k_leaf_quad_par,
+// the level kernel).
 template <bool COMPACT>
 __device__ __forceinline__ void hash_parity_node(const uint32_t (&dl)[8], const uint32_t (&dr)[8],
                                                  uint32_t (&out)[8]) {

@@ -12,9 +12,12 @@
 //              bytes (the Q0 test of nmt_wrapper.go:138-140 is symmetric), so each
 //              leaf is hashed once: 4k^2 x 9 compressions instead of the reference's
 //              8k^2 x 9. Also checks the honest push order on Q0. One square's commit.
-//   k_leaf_quad : a batch's leaves and level 1: one lane per 2x2 block of cells hashes
+//   k_leaf_quad* : a batch's leaves and level 1: one lane per 2x2 block of cells hashes
 //              its four leaves and the two row and two column nodes over them, so no
-//              leaf record is written.
+//              leaf record is written. For k >= 16 two launches, one kernel per class of
+//              tile: k_leaf_quad_q0 (the blocks inside Q0: records, namespaces, the push
+//              order) and k_leaf_quad_par (the three quarters outside: digests only);
+//              the tile numbering of each is quad_tiles.hpp. Below 16, k_leaf_quad.
 //   k_level  : one lane per inner node of one tree level, all 4k trees at once.
 //   k_level_split : a batch's levels above level 1: the nodes outside Q0 as 32-byte digests
 //              under a hash with their constant words folded, the Q0 nodes as records.
@@ -31,6 +34,7 @@
 #include "cel_internal.hpp"
 #include "nmt_device.hpp"
 #include "nmt_host.hpp"
+#include "quad_tiles.hpp"
 #include "sha256_device.hpp"
 
 namespace cel {
@@ -211,32 +215,45 @@ __global__ __launch_bounds__(256) void k_level_split(const uint32_t* __restrict_
 // hash_node site: unrolled, the kernel is 32 compression bodies of straight-line code,
 // several times the instruction cache, with every wave at another place in it.
 //   A wave is an 8x8 tile of blocks (narrower squares: k wide, 64/k block rows): row and
-// column nodes both leave it as runs of 8 records, 768 bytes, per tree. The tile lies
-// wholly inside or outside Q0 for k >= 16, so the wave-uniform parity paths of leaf_hash
-// and hash_node fire as in k_leaf / k_level. The push-order check is k_leaf's, per cell.
-//   Built for three waves per SIMD: 133 VGPRs, no scratch (ORDER, no prefetch; 151 before
-// the parity nodes had a hash of their own, measured as follows). Against
-// that, the headline step is ~2.5 % slower with the kernel held to four waves (128 VGPRs,
-// 10 dwords spilled around the node hashes), ~4 % at five (96 VGPRs, 39 spilled) and ~3 %
-// left alone (206 VGPRs, two waves): profiles/r7_leaf_quad_waves.txt.
-//   A level-1 node outside Q0 (its left leaf is; the tile's lanes all are for k >= 16) is
-// hashed by hash_parity_node from the two leaf digests and leaves as a digest into pout;
-// a Q0 node goes through hash_node and leaves as a record into out (split levels, above).
-//   grid: x = 256 blocks, y = square. ROOTS: W = 2, the one block's level-1 nodes are the
-// four roots, all through hash_node (out = roots [sq][4], put_root as k_level's last level).
-template <bool ORDER, bool PF, bool ROOTS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad(
-    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, uint32_t* __restrict__ pout,
-    int32_t* __restrict__ bad_axis, uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out,
-    uint8_t* __restrict__ col_out) {
+// column nodes both leave it as runs of 8 records, 768 bytes, per tree. The push-order
+// check is k_leaf's, per cell.
+//   A level-1 node outside Q0 (its left leaf is) is hashed by hash_parity_node from the two
+// leaf digests and leaves as a digest into pout; a Q0 node goes through hash_node and leaves
+// as a record into out (split levels, above).
+//   The tile lies wholly inside or outside Q0 for k >= 16, and there each class has a
+// kernel of its own, each wave one tile of its class (quad_tiles.hpp):
+//   k_leaf_quad_par : no class tests, no records, no hash_node, no order check: every leaf
+//              starts block 0 from kLeafParMid, every node is hash_parity_node with all 64
+//              rounds unrolled. Three quarters of a batch's lanes.
+//   k_leaf_quad_q0  : every cell is Q0; leaf_hash and hash_node have one form of block 0
+//              each (a Q0 share that carries 0xFF*29 is hashed like any other, to the same
+//              bytes), and the push-order check as before.
+//   k_leaf_quad     : k < 16, where a tile mixes the classes: the class per lane, the
+//              wave-uniform parity starts of leaf_hash and hash_node where a wave allows,
+//              hash_parity_node with rounds 32..63 rolled. ROOTS: W = 2, the one block's
+//              level-1 nodes are the four roots, all through hash_node (out = roots [sq][4],
+//              put_root as k_level's last level).
+// One kernel for both classes was 64,316 bytes of code against a 64 KB instruction cache
+// (hence the rolled rounds) and 133 VGPRs, three waves per SIMD, with every wave using half
+// of it. Apart, the parity kernel is 45,396 bytes and 86 VGPRs, the Q0 kernel 33,240 and 152
+// (ORDER, no prefetch; profiles/quad_split_isa.txt), both without scratch.
+//   Waves per SIMD: the Q0 kernel and the mixed one are built for three (held to four the
+// mixed kernel spilled 10 dwords and the headline step was ~2.5 % slower, ~4 % at five,
+// ~3 % left alone at two: profiles/r7_leaf_quad_waves.txt). The parity kernel fits four and
+// five without a spill and is still built for three: on the headline step four waves were
+// 0.7 % slower and five 1.4 %, ranges apart each time (profiles/quad_split_ab.txt).
+//   quad_block is the lane's work for all three; C says what the kernel knows of its cells.
+template <Cells C, bool ORDER, bool PF, bool ROOTS>
+__device__ __forceinline__ void quad_block(const uint8_t* __restrict__ eds, uint32_t k, uint32_t sq, uint32_t bi,
+                                           uint32_t bj, uint32_t* __restrict__ out, uint32_t* __restrict__ pout,
+                                           int32_t* __restrict__ bad_axis, uint32_t* __restrict__ leafd,
+                                           uint8_t* __restrict__ row_out, uint8_t* __restrict__ col_out) {
+  static_assert(C == Cells::kAny || !ROOTS, "the roots case is a mixed block");
   const uint32_t W = 2 * k, trees = 2 * W;
-  const uint32_t tw = k < 8 ? k : 8u, th = 64 / tw, tiles_x = k / tw;
-  const uint32_t g = blockIdx.x * 256u + threadIdx.x, tile = g / 64, l = g % 64;
-  const uint32_t bi = (tile / tiles_x) * th + l / tw, bj = (tile % tiles_x) * tw + l % tw;
-  if (bi >= k) return;
   const uint64_t sq_eds = (uint64_t)W * W * kShare;
   const uint32_t* sh00 =
-      reinterpret_cast<const uint32_t*>(eds + blockIdx.y * sq_eds + ((uint64_t)(2 * bi) * W + 2 * bj) * kShare);
+      reinterpret_cast<const uint32_t*>(eds + sq * sq_eds + ((uint64_t)(2 * bi) * W + 2 * bj) * kShare);
+  auto in_q0 = [&](uint32_t r, uint32_t c) { return C == Cells::kAny ? (r < k) && (c < k) : C == Cells::kQ0; };
   // leaf digests (SHA state words): dA of cell 00, then, 00 being done with, of cell 11;
   // dB of cell 01, dC of cell 10
   uint32_t dA[8], dB[8], dC[8];
@@ -244,10 +261,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   for (uint32_t s = 0; s < 4; s++) {  // cell s = (s >> 1, s & 1) of the block
     const uint32_t r = 2 * bi + (s >> 1), c = 2 * bj + (s & 1);
     const uint32_t* sh = sh00 + ((uint64_t)(s >> 1) * W + (s & 1)) * (kShare / 4);
-    const bool q0 = (r < k) && (c < k);
+    const bool q0 = in_q0(r, c);
     {
       uint32_t st[8];
-      leaf_hash<PF>(st, sh, q0);
+      leaf_hash<PF, C>(st, sh, q0);
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         if (s == 0 || s == 3) dA[i] = st[i];
@@ -263,7 +280,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       const uint32_t lc = s < 3 ? 0u : 1u + n;  // the left child's cell
       const bool row = (s == 1) || (s == 3 && n == 1);
       const uint32_t* shl = sh00 + ((uint64_t)(lc >> 1) * W + (lc & 1)) * (kShare / 4);
-      const bool q0l = (2 * bi + (lc >> 1) < k) && (2 * bj + (lc & 1) < k);
+      const bool q0l = in_q0(2 * bi + (lc >> 1), 2 * bj + (lc & 1));
       const uint32_t t = row ? r : W + c, idx = row ? bj : bi;  // the node's tree and index in level 1
       auto children = [&](uint32_t (&dl)[8], uint32_t (&dr)[8]) {
 #pragma unroll
@@ -279,28 +296,67 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
           children(dl, dr);
           leaf_record(shl, q0l, dl, L);
           leaf_record(sh, q0, dr, R);
-          hash_node(L, R, o);
+          hash_node<C == Cells::kAny>(L, R, o);
         }
         if (ROOTS) {
-          store_node(out + (((uint64_t)blockIdx.y * trees + t) * k + idx) * kNodeWords, o);
-          put_root(o, blockIdx.y, t, W, leafd, row_out, col_out);
+          store_node(out + (((uint64_t)sq * trees + t) * k + idx) * kNodeWords, o);
+          put_root(o, sq, t, W, leafd, row_out, col_out);
         } else {
-          store_node(out + ((uint64_t)blockIdx.y * q_nodes(k, k) + q_node(k, k, t, idx)) * kNodeWords, o);
+          store_node(out + ((uint64_t)sq * q_nodes(k, k) + q_node(k, k, t, idx)) * kNodeWords, o);
         }
       } else {
         uint32_t dl[8], dr[8], o[8];
         children(dl, dr);
-        hash_parity_node<true>(dl, dr, o);
-        store_digest(pout + ((uint64_t)blockIdx.y * p_nodes(k, k) + p_node(k, k, t, idx)) * 8, o);
+        hash_parity_node<C == Cells::kAny>(dl, dr, o);
+        store_digest(pout + ((uint64_t)sq * p_nodes(k, k) + p_node(k, k, t, idx)) * 8, o);
       }
     }
     // after the hashes, as in k_leaf: done first, the share prefixes stay live across them
     __builtin_amdgcn_sched_barrier(0);
     if (ORDER && q0) {
-      if (c > 0 && ns_less(sh, sh - kShare / 4)) atomicMin(bad_axis + blockIdx.y, (int32_t)r);
-      if (r > 0 && ns_less(sh, sh - (uint64_t)W * kShare / 4)) atomicMin(bad_axis + blockIdx.y, (int32_t)(W + c));
+      if (c > 0 && ns_less(sh, sh - kShare / 4)) atomicMin(bad_axis + sq, (int32_t)r);
+      if (r > 0 && ns_less(sh, sh - (uint64_t)W * kShare / 4)) atomicMin(bad_axis + sq, (int32_t)(W + c));
     }
   }
+}
+
+// k < 16. grid: x = 256 blocks, y = square.
+template <bool ORDER, bool PF, bool ROOTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad(
+    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, uint32_t* __restrict__ pout,
+    int32_t* __restrict__ bad_axis, uint32_t* __restrict__ leafd, uint8_t* __restrict__ row_out,
+    uint8_t* __restrict__ col_out) {
+  const uint32_t tw = k < 8 ? k : 8u, th = 64 / tw, tiles_x = k / tw;
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x, tile = g / 64, l = g % 64;
+  const uint32_t bi = (tile / tiles_x) * th + l / tw, bj = (tile % tiles_x) * tw + l % tw;
+  if (bi >= k) return;
+  quad_block<Cells::kAny, ORDER, PF, ROOTS>(eds, k, blockIdx.y, bi, bj, out, pout, bad_axis, leafd, row_out, col_out);
+}
+
+// k >= 16, the Q0 tiles. grid: x = quad::groups_for(quad::q0_tiles(k)), y = square.
+template <bool ORDER, bool PF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad_q0(
+    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ out, int32_t* __restrict__ bad_axis) {
+  const uint32_t g = blockIdx.x * quad::kGroupLanes + threadIdx.x;
+  const uint32_t tile = g / quad::kTileLanes, l = g % quad::kTileLanes;
+  if (tile >= quad::q0_tiles(k)) return;
+  const quad::TilePos at = quad::q0_tile(tile, k);
+  quad_block<Cells::kQ0, ORDER, PF, false>(eds, k, blockIdx.y, at.row * quad::kTileSide + l / quad::kTileSide,
+                                           at.col * quad::kTileSide + l % quad::kTileSide, out, nullptr, bad_axis,
+                                           nullptr, nullptr, nullptr);
+}
+
+// k >= 16, the parity tiles. grid: x = quad::groups_for(quad::par_tiles(k)), y = square.
+template <bool PF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_leaf_quad_par(
+    const uint8_t* __restrict__ eds, uint32_t k, uint32_t* __restrict__ pout) {
+  const uint32_t g = blockIdx.x * quad::kGroupLanes + threadIdx.x;
+  const uint32_t tile = g / quad::kTileLanes, l = g % quad::kTileLanes;
+  if (tile >= quad::par_tiles(k)) return;
+  const quad::TilePos at = quad::par_tile(tile, k);
+  quad_block<Cells::kParity, false, PF, false>(eds, k, blockIdx.y, at.row * quad::kTileSide + l / quad::kTileSide,
+                                               at.col * quad::kTileSide + l % quad::kTileSide, nullptr, pout, nullptr,
+                                               nullptr, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------ RFC-6962
@@ -533,8 +589,9 @@ hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uin
   return commit_levels(commit_work(work, k, nsq), k, nsq, row_roots, col_roots, dah, status, s, host_out, out_bytes);
 }
 
-// Leaves and level 1 of every square in one launch (k_leaf_quad): level 1's Q records and
-// P digests into q[0] / p[0]; at k = 1 the roots.
+// Leaves and level 1 of every square: level 1's Q records and P digests into q[0] / p[0], by
+// k_leaf_quad_q0 and k_leaf_quad_par for k >= 16, by the one k_leaf_quad below; at k = 1 the
+// roots.
 static hipError_t launch_commit_quads(const uint8_t* eds, uint32_t k, uint32_t nsq, const CommitWork& w,
                                       bool order_check, uint8_t* row_roots, uint8_t* col_roots, bool want_dah,
                                       hipStream_t s) {
@@ -553,9 +610,23 @@ static hipError_t launch_commit_quads(const uint8_t* eds, uint32_t k, uint32_t n
                          row_roots, col_roots);
     return hipGetLastError();
   }
-  dispatch_order_pf(order_check, latency_bound(lanes * nsq), [&](auto order, auto pf) {
-    hipLaunchKernelGGL((k_leaf_quad<decltype(order)::value, decltype(pf)::value, false>), g, dim3(256), 0, s, eds, k,
-                       w.q[0], w.p[0], w.bad, nullptr, nullptr, nullptr);
+  if (!quad::split_width(k)) {  // a wave's tile mixes Q0 and parity blocks
+    dispatch_order_pf(order_check, latency_bound(lanes * nsq), [&](auto order, auto pf) {
+      hipLaunchKernelGGL((k_leaf_quad<decltype(order)::value, decltype(pf)::value, false>), g, dim3(256), 0, s, eds,
+                         k, w.q[0], w.p[0], w.bad, nullptr, nullptr, nullptr);
+    });
+    return hipGetLastError();
+  }
+  // A kernel per tile class, each with its own code size and register budget. Each launch
+  // takes the prefetching leaf hash by its own lane count: the two run one after the other.
+  const uint32_t gq = quad::groups_for(quad::q0_tiles(k)), gp = quad::groups_for(quad::par_tiles(k));
+  dispatch_order_pf(order_check, latency_bound((uint64_t)gq * quad::kGroupLanes * nsq), [&](auto order, auto pf) {
+    hipLaunchKernelGGL((k_leaf_quad_q0<decltype(order)::value, decltype(pf)::value>), dim3(gq, nsq),
+                       dim3(quad::kGroupLanes), 0, s, eds, k, w.q[0], w.bad);
+  });
+  dispatch_order_pf(false, latency_bound((uint64_t)gp * quad::kGroupLanes * nsq), [&](auto, auto pf) {
+    hipLaunchKernelGGL((k_leaf_quad_par<decltype(pf)::value>), dim3(gp, nsq), dim3(quad::kGroupLanes), 0, s, eds, k,
+                       w.p[0]);
   });
   return hipGetLastError();
 }
