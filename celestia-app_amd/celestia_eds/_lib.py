@@ -43,6 +43,8 @@ EXPORTS = [
     "cel_probe_rs_transform",
     "cel_nmt_verify_batch", "cel_dev_nmt_verify_workspace_size", "cel_dev_nmt_verify_batch",
     "cel_dev_place_samples", "cel_repair_samples",
+    "cel_dev_tree_index_size", "cel_dev_tree_index_build", "cel_prove_offsets", "cel_prove_last_error",
+    "cel_dev_prove_workspace_size", "cel_dev_prove_batch", "cel_prove_samples", "cel_prove_ranges",
 ]
 
 _lib = None
@@ -138,6 +140,14 @@ def load():
             "cel_dev_nmt_verify_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, u32, P, P, P, P]),
             "cel_dev_place_samples": (i32, [P, P, P, u32, P, P, u32, P, P, P, P, P, P, P]),
             "cel_repair_samples": (i32, [P, u32, P, P, u32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+            "cel_dev_tree_index_size": (sz, [u32]),
+            "cel_dev_tree_index_build": (i32, [P, P, u32, P, P, P, P, P, u32, P]),
+            "cel_prove_offsets": (i32, [u32, u32, P, P, P, P]),
+            "cel_prove_last_error": (ctypes.c_char_p, []),
+            "cel_dev_prove_workspace_size": (sz, [u32]),
+            "cel_dev_prove_batch": (i32, [P, P, P, u32, u32, P, P, P, P, P, P, P, P]),
+            "cel_prove_samples": (i32, [P, P, u32, u32, P, P, P, P, P, P]),
+            "cel_prove_ranges": (i32, [P, P, u32, u32, P, P, P, P, P, P]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(l, name)

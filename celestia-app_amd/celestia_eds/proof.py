@@ -18,6 +18,11 @@ A node that reconstructs squares or validates many ShareProofs checks tens of th
 NMT proofs per square: VerifyInclusionBatch / VerifyShareProofs run those on the device
 (cel_nmt_verify_batch), with the host verifier above as their checker.
 
+A node that serves samples or many ShareProofs of one square builds them in batches:
+TreeIndex keeps the square and every node of its 4k trees on the device
+(cel_dev_tree_index_build) and cel_dev_prove_batch selects and packs the nodes of any number
+of range proofs there; NewShareInclusionProofsBatch builds many ShareProofs that way.
+
 Wire format (proto/celestia/core/v1/proof/proof.proto:8-49, gogoproto-generated
 pkg/proof/proof.pb.go): ShareProof / RowProof / NMTProof / Proof .Marshal() and
 Unmarshal(bytes), the bytes QueryTxInclusionProof / QueryShareInclusionProof return
@@ -543,6 +548,157 @@ def NewShareInclusionProof(ods_shares, namespace, share_start, share_end):
     """pkg/proof/proof.go:64-76: extend the ODS on the device, then prove."""
     from . import da
     return NewShareInclusionProofFromEDS(da.ExtendShares(ods_shares), namespace, share_start, share_end)
+
+
+# ------------------------------------------------------- batched construction
+def prove_offsets(k, starts, ends):
+    """cel_prove_offsets: (leaf_off, node_off), the prefix sums of each range's leaves and of
+    its ProveRange node count over 2k leaves. A bad range raises CelError naming the proof."""
+    l = _lib.load()
+    starts, ends = np.ascontiguousarray(starts, np.int32), np.ascontiguousarray(ends, np.int32)
+    n = len(starts)
+    leaf_off, node_off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    st = l.cel_prove_offsets(k, n, _p(starts), _p(ends), _p(leaf_off), _p(node_off))
+    if st != _lib.OK:
+        raise CelError(st, l.cel_prove_last_error().decode())
+    return leaf_off, node_off
+
+
+class TreeIndex:
+    """A square resident on the device with every node of its 4k row and column NMTs
+    (cel_dev_tree_index_build), for proofs in batches (cel_dev_prove_batch): one upload and
+    one hashing pass serve any number of range proofs and samples, where axis_trees +
+    nmt_prove_range download every node and pick one proof per call. `eds`: an
+    ExtendedDataSquare or a (2k, 2k, 512) uint8 array, any cells. PyTorch holds the device
+    memory and the stream, as in device.py."""
+
+    def __init__(self, eds, ctx=None, order_check=False):
+        import torch
+        cells = np.ascontiguousarray(getattr(eds, "cells", eds), dtype=np.uint8)
+        if cells.ndim != 3 or cells.shape[0] != cells.shape[1] or cells.shape[2] != _lib.SHARE_SIZE:
+            raise CelError(_lib.EINVAL, f"need a (2k, 2k, {_lib.SHARE_SIZE}) square, got {cells.shape}")
+        self.ctx = ctx or getattr(eds, "_ctx", None) or _lib.default_context()
+        self.cells = cells
+        self.w = cells.shape[0]
+        self.k = self.w // 2
+        self._torch = torch
+        self._dev = torch.device("cuda", self.ctx.device)
+        self._stream = torch.cuda.Stream(device=self._dev)
+        c, w = self.ctx, self.w
+        size = c.lib.cel_dev_tree_index_size(self.k)
+        if size == 0 or 2 * self.k != w:
+            raise CelError(_lib.ENOTPOW2, f"square width is not a power of 2: got {w / 2:g}")
+        with torch.cuda.stream(self._stream):
+            self.d_eds = torch.as_tensor(cells).to(self._dev)
+            self.d_index = torch.empty((size,), dtype=torch.uint8, device=self._dev)
+            d_roots = torch.empty((2, w, NODE), dtype=torch.uint8, device=self._dev)
+            d_dah = torch.empty((32,), dtype=torch.uint8, device=self._dev)
+            status = ctypes.c_int32(-1)
+            c.check(c.lib.cel_dev_tree_index_build(c.handle, self._ptr(self.d_eds), self.k, self._ptr(self.d_index),
+                                                   self._ptr(d_roots[0]), self._ptr(d_roots[1]), self._ptr(d_dah),
+                                                   ctypes.byref(status), _lib.FLAG_ORDER_CHECK if order_check else 0,
+                                                   self._stream_ptr()))
+            self._stream.synchronize()
+            roots = d_roots.cpu().numpy()
+            self.dah = d_dah.cpu().numpy().tobytes()
+        self.d_row_roots, self.d_col_roots = d_roots[0], d_roots[1]
+        if status.value != _lib.OK:
+            raise CelError(status.value, "invalid push order: a namespace is smaller than the previous one")
+        self.row_roots = [r.tobytes() for r in roots[0]]
+        self.col_roots = [r.tobytes() for r in roots[1]]
+
+    @staticmethod
+    def _ptr(t):
+        return ctypes.c_void_p(t.data_ptr())
+
+    def _stream_ptr(self):
+        return ctypes.c_void_p(self._stream.cuda_stream)
+
+    def prove_flat(self, axes, index, starts, ends, shares=True):
+        """One cel_dev_prove_batch: (leaves [total leaves][512] or None, nodes [total nodes][90],
+        leaf_off, node_off) as host arrays, the flat layout of cel_nmt_verify_batch."""
+        torch, c = self._torch, self.ctx
+        axes, index = np.ascontiguousarray(axes, np.uint8), np.ascontiguousarray(index, np.uint32)
+        starts, ends = np.ascontiguousarray(starts, np.int32), np.ascontiguousarray(ends, np.int32)
+        n = len(axes)
+        if not (len(index) == len(starts) == len(ends) == n):
+            raise CelError(_lib.EINVAL, "axes, index, starts and ends differ in number")
+        leaf_off, node_off = prove_offsets(self.k, starts, ends)
+        tl, tn = int(leaf_off[-1]), int(node_off[-1])
+        with torch.cuda.stream(self._stream):
+            d_leaves = torch.empty((tl, _lib.SHARE_SIZE), dtype=torch.uint8, device=self._dev) if shares else None
+            d_nodes = torch.empty((max(tn, 1), NODE), dtype=torch.uint8, device=self._dev)  # whole-tree ranges: none
+            d_work = torch.empty((c.lib.cel_dev_prove_workspace_size(n),), dtype=torch.uint8, device=self._dev)
+            c.check(c.lib.cel_dev_prove_batch(c.handle, self._ptr(self.d_eds), self._ptr(self.d_index), self.k, n,
+                                              _p(axes), _p(index), _p(starts), _p(ends),
+                                              self._ptr(d_leaves) if shares else None, self._ptr(d_nodes),
+                                              self._ptr(d_work), self._stream_ptr()))
+            self._stream.synchronize()
+            return (d_leaves.cpu().numpy() if shares else None), d_nodes[:tn].cpu().numpy(), leaf_off, node_off
+
+    def prove_ranges(self, axes, index, starts, ends, shares=False):
+        """nmt ProveRange(starts[i], ends[i]) on row (axes[i] = 0) or column (1) index[i]: a list of
+        NMTProof; with shares=True also the list of each proof's raw shares."""
+        leaves, nodes, leaf_off, node_off = self.prove_flat(axes, index, starts, ends, shares=shares)
+        proofs = [NMTProof(Start=int(s), End=int(e), Nodes=[nodes[j].tobytes() for j in range(int(a), int(b))])
+                  for s, e, a, b in zip(starts, ends, node_off[:-1], node_off[1:])]
+        if not shares:
+            return proofs
+        return proofs, [[leaves[j].tobytes() for j in range(int(a), int(b))]
+                        for a, b in zip(leaf_off[:-1], leaf_off[1:])]
+
+    def prove_samples(self, coords_axes):
+        """Samples (row, col, axis) -> (row, col, axis, share, nodes), RepairFromSamples' format:
+        the cell proved at leaf col of row `row` (axis 0) or at leaf row of column `col` (1)."""
+        coords = [(int(r), int(c), int(a)) for r, c, a in coords_axes]
+        for i, (r, c, a) in enumerate(coords):
+            if not (0 <= r < self.w and 0 <= c < self.w and 0 <= a <= 1):
+                raise CelError(_lib.EINVAL, f"sample {i}: cell ({r}, {c}) axis {a} outside the square of width {self.w}")
+        index = [c if a else r for r, c, a in coords]
+        starts = [r if a else c for r, c, a in coords]
+        leaves, nodes, _, node_off = self.prove_flat([a for _, _, a in coords], index, starts,
+                                                     [s + 1 for s in starts])
+        return [(r, c, a, leaves[i].tobytes(), [nodes[j].tobytes() for j in range(int(node_off[i]), int(node_off[i + 1]))])
+                for i, (r, c, a) in enumerate(coords)]
+
+
+def NewShareInclusionProofsBatch(eds, requests, ctx=None):
+    """NewShareInclusionProofFromEDS(eds, namespace, start, end) for every (namespace, start,
+    end) of `requests`, from one tree index: each request splits into per-row ranges as
+    CreateShareToRowRootProofs does, and all of them are one cel_dev_prove_batch. The row
+    proofs come from the RFC-6962 tree over the roots as before (32 KB at k = 128)."""
+    k = eds.Width() // 2
+    requests = [(bytes(ns), int(s), int(e)) for ns, s, e in requests]
+    for _, s, e in requests:
+        if not 0 <= s < e <= k * k:
+            raise CelError(_lib.EINVAL, f"share range [{s}, {e}) outside the {k}x{k} square")
+    if not requests:
+        return []
+    index = TreeIndex(eds, ctx=ctx or eds.ctx)
+    roots = eds.RowRoots()
+    levels = dah_tree(eds, ctx=ctx)
+    n = 4 * k
+    rows, starts, ends, spans = [], [], [], []
+    for _, s, e in requests:
+        start_row, end_row = s // k, (e - 1) // k
+        spans.append((len(rows), start_row, end_row))
+        for r in range(start_row, end_row + 1):
+            if index.row_roots[r] != roots[r]:
+                raise CelError(_lib.EINVAL, "eds row root is different than tree root")
+            rows.append(r)
+            starts.append(s % k if r == start_row else 0)
+            ends.append((e - 1) % k + 1 if r == end_row else k)  # the ODS part of the row
+    proofs, shares = index.prove_ranges([0] * len(rows), rows, starts, ends, shares=True)
+    out = []
+    for (ns, _, _), (at, start_row, end_row) in zip(requests, spans):
+        cnt = end_row - start_row + 1
+        row_proofs = [Proof(Total=n, Index=r, LeafHash=levels[r].tobytes(), Aunts=merkle_aunts(levels, n, r))
+                      for r in range(start_row, end_row + 1)]
+        out.append(ShareProof(Data=[x for leaves in shares[at:at + cnt] for x in leaves],
+                              ShareProofs=proofs[at:at + cnt], NamespaceId=ns[1:], NamespaceVersion=ns[0],
+                              RowProof=RowProof(RowRoots=[roots[r] for r in range(start_row, end_row + 1)],
+                                                Proofs=row_proofs, StartRow=start_row, EndRow=end_row)))
+    return out
 
 
 TX_NAMESPACE = bytes(28) + b"\x01"

@@ -6,6 +6,7 @@ Mirrors the pieces of github.com/celestiaorg/rsmt2d that celestia-app uses
   ComputeExtendedDataSquare, ImportExtendedDataSquare, ExtendedDataSquare.{RowRoots,
   ColRoots, Row, Col, GetCell, Flattened, Width, Repair}
   RepairFromSamples: cells with NMT inclusion proofs, verified on the device, then Repair
+  ExtendedDataSquare.SampleProofs: the producer of such samples, one device batch
 All arithmetic runs in libcelestia_eds.so (HIP); this module marshals bytes.
 
 Tree constructors. rsmt2d computes each axis root through the TreeConstructorFn it
@@ -171,6 +172,33 @@ class ExtendedDataSquare:
                 self.ctx.check(self.ctx.lib.cel_axis_root(self.ctx.handle, _p(cells), w // 2, i,
                                                           _lib.SHARE_SIZE, _p(out[i]), 0))
         self._row_roots, self._col_roots = rr, cr
+
+    def SampleProofs(self, coords):
+        """Samples of this square with their single-leaf NMT proofs, in one device batch
+        (cel_prove_samples: upload, tree index, proofs, download). coords: (row, col, axis)
+        each; returns (row, col, axis, share, nodes) each, RepairFromSamples' format: the cell
+        proved against RowRoots()[row] at leaf col (axis Row) or against ColRoots()[col] at leaf
+        row (axis Col) under the default wrapper trees. A coordinate outside the square or an
+        axis other than Row / Col raises CelError(EINVAL)."""
+        coords = [(int(r), int(c), int(a)) for r, c, a in coords]
+        if not coords:
+            return []
+        w, share, node = self.Width(), _lib.SHARE_SIZE, _lib.NMT_NODE_SIZE
+        for i, (r, c, a) in enumerate(coords):
+            if not (0 <= r < w and 0 <= c < w and a in (Row, Col)):
+                raise CelError(_lib.EINVAL, f"sample {i}: cell ({r}, {c}) axis {a} outside the square of width {w}")
+        n, per = len(coords), w.bit_length() - 1  # a single-leaf proof has log2(2k) nodes
+        rows = np.array([r for r, _, _ in coords], np.uint32)
+        cols = np.array([c for _, c, _ in coords], np.uint32)
+        axes = np.array([a for _, _, a in coords], np.uint8)
+        cells = np.ascontiguousarray(self.cells, dtype=np.uint8)
+        shares = np.zeros((n, share), np.uint8)
+        nodes = np.zeros((max(n * per, 1), node), np.uint8)
+        node_off = np.zeros(n + 1, np.uint64)
+        self.ctx.check(self.ctx.lib.cel_prove_samples(self.ctx.handle, _p(cells), w // 2, n, _p(rows), _p(cols),
+                                                      _p(axes), _p(shares), _p(nodes), _p(node_off)))
+        return [(r, c, a, shares[i].tobytes(), [nodes[j].tobytes() for j in range(int(node_off[i]), int(node_off[i + 1]))])
+                for i, (r, c, a) in enumerate(coords)]
 
     def Repair(self, row_roots, col_roots, present=None):
         """Fill every missing cell (present mask False) and verify against the roots.

@@ -25,7 +25,9 @@
 // Nodes live on the device as 96-byte records (90 B node + 6 zero bytes) = 24 dwords; a
 // slab's row-subtree records carry a mark in dword 23 (k_slab_status).
 //
-// This file is the EDS commit. The row-sharded mode is nmt_slab.hip; single trees, the
+// This file is the EDS commit, and the build of a square's tree index (launch_tree_index: the
+// single-square commit with every level kept, nmt_prove.hpp; the proofs from it are
+// nmt_prove.hip). The row-sharded mode is nmt_slab.hip; single trees, the
 // repair's axes roots, exported trees and the byte-slice hash are nmt_trees.hip.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +36,7 @@
 #include "cel_internal.hpp"
 #include "nmt_device.hpp"
 #include "nmt_host.hpp"
+#include "nmt_prove.hpp"
 #include "quad_tiles.hpp"
 #include "sha256_device.hpp"
 
@@ -525,6 +528,28 @@ static CommitWork commit_work(void* work, uint32_t k, uint32_t nsq) {
 
 size_t nmt_workspace_size(uint32_t k, uint32_t nsq) { return commit_work(nullptr, k, nsq).size; }
 
+// k_leaf over cells [c0, c1) of nsq squares: the leaf records into `leaves` ([nsq][W * W]), the
+// push-order flags into `bad`. The commit's workspace and the tree index (nmt_prove.hpp) each
+// pass their own places.
+static void launch_leaf(const uint8_t* eds, uint32_t k, uint32_t nsq, uint32_t* leaves, int32_t* bad,
+                        bool order_check, uint32_t c0, uint32_t c1, hipStream_t s) {
+  dim3 gl((c1 - c0 + 255) / 256, nsq);
+  dispatch_order_pf(order_check, latency_bound((uint64_t)(c1 - c0) * nsq), [&](auto order, auto pf) {
+    hipLaunchKernelGGL((k_leaf<decltype(order)::value, decltype(pf)::value>), gl, dim3(256), 0, s, eds, k, leaves,
+                       bad, c0, c1);
+  });
+}
+
+// k_level: the level of nin / 2 nodes per tree over `src` (the leaf records if from_leaves,
+// else a level of nin nodes per tree) into `out`; ld, ro, co: the root level's outputs.
+static void launch_level(bool from_leaves, const uint32_t* src, uint32_t* out, uint32_t W, uint32_t nin,
+                         uint32_t nsq, uint32_t* ld, uint8_t* ro, uint8_t* co, hipStream_t s) {
+  const uint32_t trees = 2 * W;
+  dim3 g((trees * (nin / 2) + 255) / 256, nsq);
+  if (from_leaves) hipLaunchKernelGGL(k_level<true>, g, dim3(256), 0, s, src, out, W, nin, trees, ld, ro, co);
+  else hipLaunchKernelGGL(k_level<false>, g, dim3(256), 0, s, src, out, W, nin, trees, ld, ro, co);
+}
+
 hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, void* work, bool order_check,
                                 uint32_t row0, uint32_t row1, bool init_bad, hipStream_t s) {
   if (quad_path(nsq)) return hipErrorInvalidValue;  // no leaf area in that workspace
@@ -534,11 +559,7 @@ hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, vo
   if (init_bad) launch_fill_i32(w.bad, nsq, INT_MAX, 256, s);
   const uint32_t c0 = row0 * W, c1 = row1 * W;
   if (c1 <= c0) return hipGetLastError();
-  dim3 gl((c1 - c0 + 255) / 256, nsq);
-  dispatch_order_pf(order_check, latency_bound((uint64_t)(c1 - c0) * nsq), [&](auto order, auto pf) {
-    hipLaunchKernelGGL((k_leaf<decltype(order)::value, decltype(pf)::value>), gl, dim3(256), 0, s, eds, k, w.leaves,
-                       w.bad, c0, c1);
-  });
+  launch_leaf(eds, k, nsq, w.leaves, w.bad, order_check, c0, c1, s);
   return hipGetLastError();
 }
 
@@ -559,7 +580,6 @@ static hipError_t commit_levels(const CommitWork& w, uint32_t k, uint32_t nsq, u
                                 uint8_t* col_roots, uint8_t* dah, int32_t* status, hipStream_t s, uint8_t* host_out,
                                 uint32_t out_bytes) {
   const uint32_t W = 2 * k;
-  const uint32_t trees = 2 * W;
   uint32_t nin = W;
   const uint32_t* src = w.leaves;
   uint32_t* dst = w.ping;
@@ -569,11 +589,9 @@ static hipError_t commit_levels(const CommitWork& w, uint32_t k, uint32_t nsq, u
     const uint32_t nout = nin / 2;
     uint32_t* out = (nout == 1) ? w.roots : dst;
     uint32_t* ld = (nout == 1 && dah) ? w.leafd : nullptr;  // dah == nullptr: roots only
-    dim3 g((trees * nout + 255) / 256, nsq);
     uint8_t* ro = (nout == 1) ? row_roots : nullptr;
     uint8_t* co = (nout == 1) ? col_roots : nullptr;
-    if (first) hipLaunchKernelGGL(k_level<true>, g, dim3(256), 0, s, src, out, W, nin, trees, ld, ro, co);
-    else hipLaunchKernelGGL(k_level<false>, g, dim3(256), 0, s, src, out, W, nin, trees, ld, ro, co);
+    launch_level(first, src, out, W, nin, nsq, ld, ro, co, s);
     first = false;
     src = out;
     dst = (dst == w.ping) ? w.pong : w.ping;
@@ -646,6 +664,35 @@ static hipError_t commit_levels_split(const CommitWork& w, uint32_t k, uint32_t 
   const uint32_t nr = 2 * k, bq = (nr + 255) / 256;  // 2k joins, 2k all-parity roots
   hipLaunchKernelGGL(k_level_split<true>, dim3(2 * bq, nsq), dim3(256), 0, s, w.q[at], nullptr, w.p[at], nullptr, nr,
                      nr, bq, k, want_dah ? w.leafd : nullptr, row_roots, col_roots);
+  return hipGetLastError();
+}
+
+// The tree index of one square (nmt_prove.hpp): the single-square commit's launches with
+// every level kept, level l written at its own place in d_index. A caller that wants no DAH
+// still gets its status: the DAH then goes to the index's tail.
+hipError_t launch_tree_index(const uint8_t* eds, uint32_t k, void* d_index, uint8_t* row_roots, uint8_t* col_roots,
+                             uint8_t* dah, int32_t* status, bool order_check, hipStream_t s) {
+  const prove::IndexLayout x = prove::index_layout(k);
+  uint8_t* base = static_cast<uint8_t*>(d_index);
+  auto level = [&](uint32_t l) { return reinterpret_cast<uint32_t*>(base + x.level_off[l]); };
+  uint32_t* leafd = reinterpret_cast<uint32_t*>(base + x.leafd_off);
+  int32_t* bad = reinterpret_cast<int32_t*>(base + x.bad_off);
+  if (!dah) dah = base + x.dah_off;
+  {
+    const Range r("index.leaf");
+    launch_fill_i32(bad, 1, INT_MAX, 256, s);
+    launch_leaf(eds, k, 1, level(0), bad, order_check, 0, x.W * x.W, s);
+  }
+  {
+    const Range r("index.levels");
+    for (uint32_t l = 1; l <= x.L; l++) {
+      const bool root = l == x.L;
+      launch_level(l == 1, level(l - 1), level(l), x.W, x.W >> (l - 1), 1, root ? leafd : nullptr,
+                   root ? row_roots : nullptr, root ? col_roots : nullptr, s);
+    }
+  }
+  const Range r("dah");
+  launch_merkle(level(x.L), leafd, 2 * x.W, 1, dah, bad, status, s, nullptr, nullptr, 0);
   return hipGetLastError();
 }
 

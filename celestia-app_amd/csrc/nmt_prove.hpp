@@ -1,0 +1,133 @@
+// The batched NMT prover (nmt_prove.hip, api_prove.cpp): the tree index of a resident square,
+// the closed form of nmt ProveRange's node selection, and the per-proof table the kernel
+// reads. Everything above the launcher declarations is plain C++ with no HIP in it:
+// tools/prove_select_check.cpp includes this header alone and walks it on the host.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#ifdef __HIPCC__
+#define CEL_PROVE_HD __host__ __device__
+#else
+#define CEL_PROVE_HD
+#endif
+
+namespace cel {
+namespace prove {
+
+constexpr uint32_t kRecordBytes = 96;  // a node on the device: 90 bytes and 6 zero bytes
+constexpr uint32_t kMaxLevels = 16;
+
+// ------------------------------------------------------------------ tree index
+//
+// Every node of the 4k row and column NMTs of one 2k x 2k square, as 96-byte records. With
+// W = 2k and L = log2(W):
+//   level 0      the W * W leaf records, [row][col]: the leaf of cell (r, c) is leaf c of
+//                row tree r and leaf r of column tree c, so it is stored once;
+//   level l >= 1 [2W trees][W >> l] records, the W row trees first, then the W column trees;
+//                level L holds the 2W roots.
+// Behind the records a tail the build alone uses: the roots' RFC-6962 leaf digests, a DAH
+// for a caller that wants none, the push-order flag and the status.
+
+// First record of level l (l = 0 .. L + 1; L + 1 gives the record count).
+CEL_PROVE_HD inline uint64_t index_level_rec(uint32_t W, uint32_t l) {
+  if (l == 0) return 0;
+  return (uint64_t)W * W + (uint64_t)2 * W * (W - (W >> (l - 1)));
+}
+
+// Record of node `pos` of level l of tree `index` along `axis` (0 = row, 1 = column).
+CEL_PROVE_HD inline uint64_t index_record(uint32_t W, uint32_t axis, uint32_t index, uint32_t l, uint32_t pos) {
+  if (l == 0) return axis ? (uint64_t)pos * W + index : (uint64_t)index * W + pos;
+  return index_level_rec(W, l) + (uint64_t)(axis ? W + index : index) * (W >> l) + pos;
+}
+
+struct IndexLayout {
+  uint32_t W, L;
+  uint64_t level_off[kMaxLevels];  // byte offset of level l, l = 0 .. L
+  uint64_t records;                // all levels
+  uint64_t leafd_off;              // [2W][32] RFC-6962 leaf digests of the roots
+  uint64_t dah_off;                // 32 bytes
+  uint64_t bad_off, status_off;    // int32 each
+  uint64_t bytes;
+};
+
+// k a power of two, 1 <= k <= 2048.
+inline IndexLayout index_layout(uint32_t k) {
+  IndexLayout x{};
+  x.W = 2 * k;
+  while ((1u << x.L) < x.W) x.L++;
+  for (uint32_t l = 0; l <= x.L; l++) x.level_off[l] = index_level_rec(x.W, l) * kRecordBytes;
+  x.records = index_level_rec(x.W, x.L + 1);
+  x.leafd_off = x.records * kRecordBytes;  // a multiple of 32
+  x.dah_off = x.leafd_off + (uint64_t)2 * x.W * 32;
+  x.bad_off = x.dah_off + 32;
+  x.status_off = x.bad_off + 4;
+  x.bytes = x.status_off + 4 + 8;  // to a multiple of 16
+  return x;
+}
+
+// ------------------------------------------------- ProveRange's nodes, closed form
+//
+// nmt ProveRange(start, end) over 2^L leaves lists, left to right, the roots of the maximal
+// subtrees outside [start, end) (proof.cpp: collect). With s = start and e1 = end - 1 these
+// are the left siblings along s's path, from the top down (every level l whose bit of s is
+// set: node (s >> l) ^ 1), then the right siblings along e1's path, from the bottom up
+// (every level l whose bit of e1 is clear: node (e1 >> l) ^ 1).
+
+struct NodeAt {
+  uint32_t level, pos;
+};
+
+CEL_PROVE_HD inline uint32_t node_count(uint32_t L, uint32_t s, uint32_t e1) {
+  return (uint32_t)__builtin_popcount(s) + L - (uint32_t)__builtin_popcount(e1);
+}
+
+// Node j of the proof, j < node_count(L, s, e1); {L, 0} beyond it.
+CEL_PROVE_HD inline NodeAt node_at(uint32_t L, uint32_t s, uint32_t e1, uint32_t j) {
+  const uint32_t left = (uint32_t)__builtin_popcount(s);
+  if (j < left) {
+    for (uint32_t l = L; l-- > 0;)
+      if ((s >> l) & 1u) {
+        if (j == 0) return NodeAt{l, (s >> l) ^ 1u};
+        j--;
+      }
+  } else {
+    j -= left;
+    for (uint32_t l = 0; l < L; l++)
+      if (!((e1 >> l) & 1u)) {
+        if (j == 0) return NodeAt{l, (e1 >> l) ^ 1u};
+        j--;
+      }
+  }
+  return NodeAt{L, 0};
+}
+
+// One proof of a batch as the kernel reads it: ProveRange(start, end) on tree `index` along
+// `axis`, its nodes from packed node node0 on, its shares from share leaf0 on.
+struct Request {
+  uint32_t axis, index;
+  int32_t start, end;
+  uint64_t node0, leaf0;
+};
+static_assert(sizeof(Request) == 32, "Request layout");
+
+}  // namespace prove
+}  // namespace cel
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+namespace cel {
+
+// The index of the square at eds (nmt_kernels.hip: the single-square commit's leaf and level
+// kernels, every level written to its own place in d_index), the packed roots, and the DAH
+// (nullable) as launch_commit gives them. status: device int32, nullable.
+hipError_t launch_tree_index(const uint8_t* eds, uint32_t k, void* d_index, uint8_t* row_roots, uint8_t* col_roots,
+                             uint8_t* dah, int32_t* status, bool order_check, hipStream_t s);
+// n proofs from d_index (nmt_prove.hip). d_req: the n requests in device memory. d_leaves
+// nullable (then eds is not read); both 16-byte aligned. d_nodes 2-byte aligned.
+hipError_t launch_prove(const uint8_t* eds, const void* d_index, uint32_t k, const prove::Request* d_req, uint32_t n,
+                        uint8_t* d_leaves, uint8_t* d_nodes, hipStream_t s);
+
+}  // namespace cel
+#endif

@@ -442,6 +442,63 @@ cel_status cel_repair_samples(cel_ctx* ctx, uint32_t k, const uint8_t* row_roots
                               uint8_t* ok_out, uint8_t* eds_out, uint8_t* present_out, int32_t* bad_axis,
                               int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present);
 
+/* ------------------------------------------------- proofs in batches, tree index
+ * nmt ProveRange (nmt v0.22.0 [dep], as pkg/proof/proof.go:190 calls it per row) for many
+ * requests over one resident square: the range proofs of ShareProofs and of sampled cells, in
+ * the layout the verifier above reads, so a producer and a verifier chain with no repacking.
+ *
+ * cel_dev_tree_index_build: every node of the 4k row and column NMTs of the square at d_eds
+ * (2k*2k*512 bytes, any cells, codeword or not, 16-byte aligned) into d_index
+ * (cel_dev_tree_index_size(k) bytes, 16-byte aligned): 96-byte records, the 2k*2k leaf
+ * records [row][col] once (a cell's leaf is the same in its row tree and its column tree),
+ * then level l = 1 .. log2(2k) as [4k trees][2k >> l], the 2k row trees first, then the
+ * columns; a tail of 64*2k + 48 bytes belongs to the build. d_row_roots / d_col_roots
+ * (2k*90 bytes each), d_dah (32 bytes, nullable) and CEL_FLAG_ORDER_CHECK as in
+ * cel_dev_commit_only for one square. status (nullable): host memory, 0 or CEL_EORDER,
+ * copied back on the stream: valid once the stream is synchronised (page-locked memory
+ * keeps the call asynchronous). k: a power of two up to 512, rejected otherwise as the other
+ * device entry points reject it; k = 1 is valid (leaves and roots).
+ * cel_dev_tree_index_size is 0 for a k that is not a power of two or is above 2048. */
+size_t cel_dev_tree_index_size(uint32_t k);
+cel_status cel_dev_tree_index_build(cel_ctx* ctx, const void* d_eds, uint32_t k, void* d_index,
+                                    void* d_row_roots, void* d_col_roots, void* d_dah,
+                                    int32_t* status, uint32_t flags, void* stream);
+/* Host only: where each proof's output goes. leaf_off[i] / node_off[i] (n + 1 entries each) are
+ * the prefix sums of ends[i] - starts[i] and of the node count of ProveRange(starts[i],
+ * ends[i]) over 2k leaves. The ranges are the caller's own, so a bad one (start < 0, end <=
+ * start, end > 2k) is CEL_EINVAL, with the proof named in cel_prove_last_error (this
+ * thread's last cel_prove_offsets failure). */
+cel_status cel_prove_offsets(uint32_t k, uint32_t n, const int32_t* starts, const int32_t* ends,
+                             uint64_t* leaf_off, uint64_t* node_off);
+const char* cel_prove_last_error(void);
+/* Proof i = ProveRange(starts[i], ends[i]) on row index[i] (axes[i] = 0) or column index[i]
+ * (axes[i] = 1) of the square whose index is d_index. Its nodes go to d_nodes + 90 *
+ * node_off[i], packed and in nmt order (the bytes cel_nmt_prove_range gives for that tree);
+ * its shares to d_leaves + 512 * leaf_off[i] (d_leaves nullable: nodes only, and d_eds is
+ * then not read), offsets as cel_prove_offsets gives them. d_leaves, d_eds, d_index and d_work
+ * 16-byte aligned, d_nodes 2-byte aligned; d_work: cel_dev_prove_workspace_size(n) bytes.
+ * The host arrays are consumed before the call returns; asynchronous on stream (NULL = the
+ * ctx's own). CEL_EINVAL: nil argument, misalignment, axes[i] > 1, index[i] >= 2k, a bad
+ * range. n = 0 is CEL_OK. */
+size_t cel_dev_prove_workspace_size(uint32_t n);
+cel_status cel_dev_prove_batch(cel_ctx* ctx, const void* d_eds, const void* d_index, uint32_t k,
+                               uint32_t n, const uint8_t* axes, const uint32_t* index,
+                               const int32_t* starts, const int32_t* ends, void* d_leaves,
+                               void* d_nodes, void* d_work, void* stream);
+/* The same for a square in host memory (eds: 2k*2k*512): upload, index, proofs, download.
+ * Synchronous. cel_prove_samples: sample i is cell (rows[i], cols[i]), proved at leaf cols[i]
+ * of row rows[i] (axes[i] = 0) or at leaf rows[i] of column cols[i] (axes[i] = 1), the
+ * convention of cel_dev_place_samples, whose shares / nodes / node_off arguments these
+ * outputs are (shares_out: n*512; nodes_out: n * log2(2k) nodes; node_off_out: n + 1). A
+ * coordinate >= 2k is CEL_EINVAL. cel_prove_ranges: the arguments of cel_dev_prove_batch,
+ * outputs sized by cel_prove_offsets (leaves_out nullable). */
+cel_status cel_prove_samples(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32_t n,
+                             const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                             uint8_t* shares_out, uint8_t* nodes_out, uint64_t* node_off_out);
+cel_status cel_prove_ranges(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32_t n,
+                            const uint8_t* axes, const uint32_t* index, const int32_t* starts,
+                            const int32_t* ends, uint8_t* leaves_out, uint8_t* nodes_out);
+
 /* Blob share commitments from an EDS (pkg/inclusion).
  * cel_commitment_paths: calculateCommitmentPaths (paths.go:16-47) for a blob of
  * blob_share_len shares placed at the first aligned index >= start of a square of
