@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("CEL_EDS_LIB", os.path.join(_ROOT, "libcelestia_eds.so
 OK, EINVAL, ENOTPOW2, ECHUNK, ETOOBIG, EORDER, ETOOFEW, EBYZANTINE, EUNREPAIRABLE, EDEVICE, ENOMEM, \
     ESHORT, EPUSHPAST, EBADROOT, ENODATA = range(15)
 FLAG_ORDER_CHECK = 0x1
+NS_INCLUSION, NS_ABSENCE = 0, 1
 FLAG_PARITY_ONLY = 0x2
 FLAG_CALLER_STREAM = 0x4
 FLAG_SHARD_EXCHANGE = 0x8
@@ -45,6 +46,9 @@ EXPORTS = [
     "cel_dev_place_samples", "cel_repair_samples",
     "cel_dev_tree_index_size", "cel_dev_tree_index_build", "cel_prove_offsets", "cel_prove_last_error",
     "cel_dev_prove_workspace_size", "cel_dev_prove_batch", "cel_prove_samples", "cel_prove_ranges",
+    "cel_dev_namespace_workspace_size", "cel_dev_namespace_plan", "cel_dev_namespace_prove", "cel_namespace_rows",
+    "cel_nmt_verify_namespace_batch", "cel_dev_nmt_verify_namespace_workspace_size",
+    "cel_dev_nmt_verify_namespace_batch",
 ]
 
 _lib = None
@@ -148,6 +152,13 @@ def load():
             "cel_dev_prove_batch": (i32, [P, P, P, u32, u32, P, P, P, P, P, P, P, P]),
             "cel_prove_samples": (i32, [P, P, u32, u32, P, P, P, P, P, P]),
             "cel_prove_ranges": (i32, [P, P, u32, u32, P, P, P, P, P, P]),
+            "cel_dev_namespace_workspace_size": (sz, [u32, u32]),
+            "cel_dev_namespace_plan": (i32, [P, P, u32, u32, P, u64, P, P, P, P, P, P, P, P, P, P]),
+            "cel_dev_namespace_prove": (i32, [P, P, P, u32, u64, P, P, P, P]),
+            "cel_namespace_rows": (i32, [P, P, u32, u32, P, u64, u64, u64] + [P] * 12),
+            "cel_nmt_verify_namespace_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, P, u32, P, P]),
+            "cel_dev_nmt_verify_namespace_workspace_size": (sz, [u64, u64, u32]),
+            "cel_dev_nmt_verify_namespace_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, P, u32, P, P, P, P]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(l, name)

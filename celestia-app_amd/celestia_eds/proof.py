@@ -23,6 +23,15 @@ TreeIndex keeps the square and every node of its 4k trees on the device
 (cel_dev_tree_index_build) and cel_dev_prove_batch selects and packs the nodes of any number
 of range proofs there; NewShareInclusionProofsBatch builds many ShareProofs that way.
 
+A node that serves a namespace ("every share of namespace N in this block, and a proof that
+none was left out": celestia-node GetSharesByNamespace) asks every row whose root range holds N
+for nmt ProveNamespace: TreeIndex.namespace_rows finds those rows and the namespace's leaves in
+them on the device, for any number of namespaces at once (cel_dev_namespace_plan /
+cel_dev_namespace_prove), and VerifyNamespaceBatch checks such proofs there
+(cel_nmt_verify_namespace_batch). NMTProof.VerifyNamespace / verify_namespace and
+nmt_prove_namespace are their host mirrors. nmt is a dependency outside the reference tree, so
+these rules are this project's restatement of nmt v0.22.0 (include/celestia_eds.h states them).
+
 Wire format (proto/celestia/core/v1/proof/proof.proto:8-49, gogoproto-generated
 pkg/proof/proof.pb.go): ShareProof / RowProof / NMTProof / Proof .Marshal() and
 Unmarshal(bytes), the bytes QueryTxInclusionProof / QueryShareInclusionProof return
@@ -83,6 +92,92 @@ def _rfc_leaf(item):
 
 def _rfc_inner(left, right):
     return _sha(b"\x01" + left + right)
+
+
+def _compute_root(start, end, hashes, nodes, nsz):
+    """nmt Proof.computeRoot over the leaf hashes of [start, end) and the proof nodes, then the
+    surplus nodes as right siblings at the top. ValueError on unordered children."""
+    state = {"nodes": list(nodes), "leaves": list(hashes)}
+
+    def pop(key):
+        lst = state[key]
+        if not lst:
+            return None
+        v = lst[0]
+        state[key] = lst[1:]
+        return v
+
+    def compute(s, e):
+        if e - s == 1:
+            return pop("leaves") if start <= s < end else pop("nodes")
+        if e <= start or s >= end:
+            return pop("nodes")
+        k = _split_point(e - s)
+        lh = compute(s, s + k)
+        rh = compute(s + k, e)
+        if rh is None:
+            return lh
+        return _nmt_node(lh, rh, nsz)
+
+    est = max(_split_point(end) * 2 if end > 1 else 1, 1)
+    h = compute(0, est)
+    for n in state["nodes"]:
+        h = _nmt_node(h, n, nsz)
+    return h
+
+
+NS_INCLUSION, NS_ABSENCE = _lib.NS_INCLUSION, _lib.NS_ABSENCE
+
+
+def verify_namespace(start, end, kind, namespace, leaves, nodes, root):
+    """nmt Proof.VerifyNamespace in the flat form the device takes (cel_nmt_verify_namespace_batch):
+    `leaves` are whole shares, and an absence proof's leaf hash is the last of `nodes`. Every
+    input is untrusted; a malformed proof is False.
+
+    empty proof  inclusion, start == end, no nodes, no leaves: True iff the namespace lies
+                 outside the root's range. Any other proof with start == end is False.
+    inclusion    0 <= start < end, end - start leaves, each share starting with the namespace
+                 (celestia-node hands nmt share[:29] || share; nmt checks that prefix).
+    absence      end == start + 1, no leaves, at least popcount(start) + 1 nodes; the leaf hash
+                 has min <= max and namespace < min, and is the single leaf folded.
+    both         of the nodes, the first popcount(start) are the left siblings of the range and
+                 each must end below the namespace; the others are right siblings and each must
+                 begin above it (completeness); the folded node equals the root."""
+    namespace, root = bytes(namespace), bytes(root)
+    nsz = len(namespace)
+    nodes = [bytes(x) for x in nodes]
+    if kind not in (NS_INCLUSION, NS_ABSENCE):
+        return False
+    if len(root) != 2 * nsz + 32 or any(len(x) != 2 * nsz + 32 for x in nodes):
+        return False
+    if start == end:
+        if kind != NS_INCLUSION or nodes or leaves:
+            return False
+        return namespace < root[:nsz] or namespace > root[nsz:2 * nsz]
+    if start < 0 or end < start:
+        return False
+    nl = bin(start).count("1")
+    if kind == NS_INCLUSION:
+        if len(leaves) != end - start or len(nodes) < nl:
+            return False
+        if any(bytes(x[:nsz]) != namespace for x in leaves):
+            return False
+        hashes = [_nmt_leaf(namespace, bytes(x)) for x in leaves]
+    else:
+        if end != start + 1 or leaves or len(nodes) < nl + 1:
+            return False
+        leaf_hash, nodes = nodes[-1], nodes[:-1]
+        if leaf_hash[:nsz] > leaf_hash[nsz:2 * nsz] or not namespace < leaf_hash[:nsz]:
+            return False
+        hashes = [leaf_hash]
+    if any(not x[nsz:2 * nsz] < namespace for x in nodes[:nl]):
+        return False
+    if any(not x[:nsz] > namespace for x in nodes[nl:]):
+        return False
+    try:
+        return _compute_root(start, end, hashes, nodes, nsz) == root
+    except (ValueError, TypeError):  # unordered children; a node missing
+        return False
 
 
 # ---------------------------------------------------------------- proto3 wire
@@ -239,37 +334,27 @@ class NMTProof:
         if start < 0 or end <= start or len(leaves) != end - start:
             return False
         hashes = [_nmt_leaf(namespace, d) for d in leaves]
-        nodes = list(self.Nodes)
-        state = {"nodes": nodes, "leaves": hashes}
-
-        def pop(key):
-            lst = state[key]
-            if not lst:
-                return None
-            v = lst[0]
-            state[key] = lst[1:]
-            return v
-
-        def compute(s, e):
-            if e - s == 1:
-                return pop("leaves") if start <= s < end else pop("nodes")
-            if e <= start or s >= end:
-                return pop("nodes")
-            k = _split_point(e - s)
-            lh = compute(s, s + k)
-            rh = compute(s + k, e)
-            if rh is None:
-                return lh
-            return _nmt_node(lh, rh, nsz)
-
-        est = max(_split_point(end) * 2 if end > 1 else 1, 1)
         try:
-            h = compute(0, est)
-            for n in state["nodes"]:
-                h = _nmt_node(h, n, nsz)
+            return _compute_root(start, end, hashes, self.Nodes, nsz) == root
         except ValueError:
             return False
-        return h == root
+
+    def IsOfAbsence(self):
+        """nmt Proof.IsOfAbsence: the proof carries a leaf hash."""
+        return bool(self.LeafHash)
+
+    def IsEmptyProof(self):
+        """nmt Proof.IsEmptyProof: the proof of a namespace outside the tree's range."""
+        return self.Start == self.End and not self.Nodes and not self.LeafHash
+
+    def VerifyNamespace(self, namespace, leaves, root):
+        """nmt Proof.VerifyNamespace: `leaves` (whole 512-byte shares) are all the leaves of
+        `namespace` under `root`, none left out; or, for an absence proof (LeafHash set, no
+        leaves) and for the empty proof, the tree holds none. verify_namespace states the rules."""
+        absent = self.IsOfAbsence()
+        nodes = list(self.Nodes) + ([bytes(self.LeafHash)] if absent else [])
+        return verify_namespace(self.Start, self.End, NS_ABSENCE if absent else NS_INCLUSION, namespace, leaves, nodes,
+                                root)
 
 
 @dataclass
@@ -495,6 +580,27 @@ def nmt_prove_range(tree, start, end):
     return [out[i].tobytes() for i in range(cnt.value)]
 
 
+def nmt_prove_namespace(tree, nleaves, namespace):
+    """nmt ProveNamespace(namespace) on one tree of axis_trees() (nleaves leaves, a power of two),
+    as celestia-node asks it of a row: None when the namespace lies outside the root's range (or
+    above every leaf); the inclusion proof of all its leaves [lt, le); or, when the tree holds
+    none, the absence proof: ProveRange(lt, lt + 1) with LeafHash = the leaf that follows where the
+    namespace would be. lt / le count the leaves whose namespace is below / not above it."""
+    namespace = bytes(namespace)
+    tree = np.ascontiguousarray(tree)
+    root = tree[-1].tobytes()
+    if not root[:NS] <= namespace <= root[NS:2 * NS]:
+        return None
+    mins = [tree[i, :NS].tobytes() for i in range(nleaves)]
+    lt = sum(1 for m in mins if m < namespace)
+    le = sum(1 for m in mins if m <= namespace)
+    if lt >= nleaves:
+        return None
+    if le > lt:
+        return NMTProof(Start=lt, End=le, Nodes=nmt_prove_range(tree, lt, le))
+    return NMTProof(Start=lt, End=lt + 1, Nodes=nmt_prove_range(tree, lt, lt + 1), LeafHash=tree[lt].tobytes())
+
+
 def merkle_aunts(levels, n, index):
     l = _lib.load()
     levels = np.ascontiguousarray(levels)
@@ -662,6 +768,59 @@ class TreeIndex:
                 for i, (r, c, a) in enumerate(coords)]
 
 
+    def namespace_flat(self, namespaces):
+        """cel_dev_namespace_plan + cel_dev_namespace_prove for `namespaces` (29 bytes each): a dict
+        of the entries' host arrays (ns_idx, rows, starts, ends, kinds, leaf_off, node_off) with
+        leaves [total shares][512] and nodes [total nodes][90], the flat layout of
+        cel_nmt_verify_namespace_batch."""
+        torch, c = self._torch, self.ctx
+        nss = [bytes(x) for x in namespaces]
+        n = len(nss)
+        if any(len(x) != NS for x in nss):
+            raise CelError(_lib.EINVAL, f"a namespace is {NS} bytes")
+        ns = np.frombuffer(b"".join(nss) or b"\0", np.uint8).copy()
+        cnt = ctypes.c_uint64(0)
+        with torch.cuda.stream(self._stream):
+            d_work = torch.empty((max(c.lib.cel_dev_namespace_workspace_size(self.k, n), 16),), dtype=torch.uint8,
+                                 device=self._dev)
+            cap = n * self.w
+            out = dict(ns_idx=np.zeros(cap, np.uint32), rows=np.zeros(cap, np.uint32), starts=np.zeros(cap, np.int32),
+                       ends=np.zeros(cap, np.int32), kinds=np.zeros(cap, np.uint8), leaf_off=np.zeros(cap + 1, np.uint64),
+                       node_off=np.zeros(cap + 1, np.uint64))
+            c.check(c.lib.cel_dev_namespace_plan(c.handle, self._ptr(self.d_index), self.k, n, _p(ns), cap,
+                                                 _p(out["ns_idx"]), _p(out["rows"]), _p(out["starts"]), _p(out["ends"]),
+                                                 _p(out["kinds"]), _p(out["leaf_off"]), _p(out["node_off"]),
+                                                 ctypes.byref(cnt), self._ptr(d_work), self._stream_ptr()))
+            m = cnt.value
+            out = {key: v[:m + 1] if key.endswith("_off") else v[:m] for key, v in out.items()}
+            tl, tn = int(out["leaf_off"][-1]), int(out["node_off"][-1])
+            d_leaves = torch.empty((max(tl, 1), _lib.SHARE_SIZE), dtype=torch.uint8, device=self._dev)
+            d_nodes = torch.empty((max(tn, 1), NODE), dtype=torch.uint8, device=self._dev)
+            c.check(c.lib.cel_dev_namespace_prove(c.handle, self._ptr(self.d_eds), self._ptr(self.d_index), self.k, m,
+                                                  self._ptr(d_leaves), self._ptr(d_nodes), self._ptr(d_work),
+                                                  self._stream_ptr()))
+            self._stream.synchronize()
+            out["leaves"], out["nodes"] = d_leaves[:tl].cpu().numpy(), d_nodes[:tn].cpu().numpy()
+        return out
+
+    def namespace_rows(self, namespaces):
+        """nmt ProveNamespace of every namespace on every row whose root range holds it: per
+        namespace a list of (row, NMTProof, shares), rows ascending. An inclusion proof comes with
+        the namespace's shares of that row; an absence proof has LeafHash set and no shares. A
+        namespace that no row's range holds gives an empty list."""
+        f = self.namespace_flat(namespaces)
+        out = [[] for _ in namespaces]
+        for e in range(len(f["rows"])):
+            a, b = int(f["node_off"][e]), int(f["node_off"][e + 1])
+            nodes = [f["nodes"][j].tobytes() for j in range(a, b)]
+            absent = int(f["kinds"][e]) == NS_ABSENCE
+            p = NMTProof(Start=int(f["starts"][e]), End=int(f["ends"][e]), Nodes=nodes[:-1] if absent else nodes,
+                         LeafHash=nodes[-1] if absent else None)
+            shares = [f["leaves"][j].tobytes() for j in range(int(f["leaf_off"][e]), int(f["leaf_off"][e + 1]))]
+            out[int(f["ns_idx"][e])].append((int(f["rows"][e]), p, shares))
+        return out
+
+
 def NewShareInclusionProofsBatch(eds, requests, ctx=None):
     """NewShareInclusionProofFromEDS(eds, namespace, start, end) for every (namespace, start,
     end) of `requests`, from one tree index: each request splits into per-row ranges as
@@ -782,6 +941,47 @@ def VerifyInclusionBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
     ctx.check(ctx.lib.cel_nmt_verify_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(ns), _p(leaves),
                                            _p(leaf_off), _p(nodes), _p(node_off), _p(rts), len(root_at), _p(ridx),
                                            _p(ok)))
+    for i, v in zip(keep, ok):
+        out[i] = bool(v)
+    return out
+
+
+def VerifyNamespaceBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
+    """NMTProof.VerifyNamespace(namespaces[i], leaves_per_proof[i], roots[i]) for every proof in one
+    device batch (cel_nmt_verify_namespace_batch): a list of bools. A proof with a non-empty
+    LeafHash is an absence proof; its leaf hash travels as the last node. Sizes other than the
+    app's are False without reaching the device, as in VerifyInclusionBatch."""
+    n = len(proofs)
+    if not (len(namespaces) == len(leaves_per_proof) == len(roots) == n):
+        raise CelError(_lib.EINVAL, "proofs, namespaces, leaves and roots differ in number")
+    out = [False] * n
+    share = _lib.SHARE_SIZE
+    nodes_of = lambda p: list(p.Nodes) + ([bytes(p.LeafHash)] if p.LeafHash else [])
+    keep = [i for i in range(n)
+            if len(namespaces[i]) == NS and len(roots[i]) == NODE
+            and -(1 << 31) <= proofs[i].Start < 1 << 31 and -(1 << 31) <= proofs[i].End < 1 << 31
+            and all(len(x) == NODE for x in nodes_of(proofs[i])) and all(len(x) == share for x in leaves_per_proof[i])]
+    if not keep:
+        return out
+    ctx = ctx or _lib.default_context()
+    root_at, root_idx = {}, []
+    for i in keep:
+        root_idx.append(root_at.setdefault(bytes(roots[i]), len(root_at)))
+    leaf_off = np.cumsum([0] + [len(leaves_per_proof[i]) for i in keep]).astype(np.uint64)
+    node_off = np.cumsum([0] + [len(nodes_of(proofs[i])) for i in keep]).astype(np.uint64)
+    buf = lambda parts: np.frombuffer(b"".join(parts) or b"\0", np.uint8).copy()
+    starts = np.array([proofs[i].Start for i in keep], np.int32)
+    ends = np.array([proofs[i].End for i in keep], np.int32)
+    kinds = np.array([NS_ABSENCE if proofs[i].LeafHash else NS_INCLUSION for i in keep], np.uint8)
+    ns = buf(bytes(namespaces[i]) for i in keep)
+    leaves = buf(bytes(x) for i in keep for x in leaves_per_proof[i])
+    nodes = buf(bytes(x) for i in keep for x in nodes_of(proofs[i]))
+    rts = buf(root_at)
+    ridx = np.array(root_idx, np.uint32)
+    ok = np.zeros(len(keep), np.uint8)
+    ctx.check(ctx.lib.cel_nmt_verify_namespace_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(kinds), _p(ns),
+                                                     _p(leaves), _p(leaf_off), _p(nodes), _p(node_off), _p(rts),
+                                                     len(root_at), _p(ridx), _p(ok)))
     for i, v in zip(keep, ok):
         out[i] = bool(v)
     return out

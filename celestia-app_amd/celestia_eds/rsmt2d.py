@@ -173,6 +173,44 @@ class ExtendedDataSquare:
                                                           _lib.SHARE_SIZE, _p(out[i]), 0))
         self._row_roots, self._col_roots = rr, cr
 
+    def SharesByNamespace(self, namespace):
+        """Every share of `namespace` (29 bytes) in this square with the proofs that none was left
+        out, what celestia-node's GetSharesByNamespace serves: for each row whose root range holds
+        the namespace, in row order, (row, NMTProof, shares) with nmt ProveNamespace's proof
+        against RowRoots()[row]: the namespace's shares of that row, or an absence proof (LeafHash
+        set, no shares). One device call (cel_namespace_rows: upload, tree index, search, proofs,
+        download). The parity namespace raises CelError(EINVAL); a square whose shares are not in
+        namespace order, CelError(EORDER)."""
+        from .proof import NMTProof
+        ns = bytes(namespace)
+        if len(ns) != _lib.NAMESPACE_SIZE:
+            raise CelError(_lib.EINVAL, f"a namespace is {_lib.NAMESPACE_SIZE} bytes")
+        c, w, share, node = self.ctx, self.Width(), _lib.SHARE_SIZE, _lib.NMT_NODE_SIZE
+        cells = np.ascontiguousarray(self.cells, dtype=np.uint8)
+        nsa = np.frombuffer(ns, np.uint8).copy()
+        cnt, tl, tn = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        c.check(c.lib.cel_namespace_rows(c.handle, _p(cells), w // 2, 1, _p(nsa), 0, 0, 0, *([None] * 9),
+                                         ctypes.byref(cnt), ctypes.byref(tl), ctypes.byref(tn)))
+        m = cnt.value
+        if m == 0:
+            return []
+        ns_idx, rows = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        starts, ends, kinds = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        leaf_off, node_off = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64)
+        leaves, nodes = np.zeros((max(tl.value, 1), share), np.uint8), np.zeros((max(tn.value, 1), node), np.uint8)
+        c.check(c.lib.cel_namespace_rows(c.handle, _p(cells), w // 2, 1, _p(nsa), m, tl.value, tn.value, _p(ns_idx),
+                                         _p(rows), _p(starts), _p(ends), _p(kinds), _p(leaf_off), _p(node_off),
+                                         _p(leaves), _p(nodes), ctypes.byref(cnt), ctypes.byref(tl), ctypes.byref(tn)))
+        out = []
+        for e in range(m):
+            nd = [nodes[j].tobytes() for j in range(int(node_off[e]), int(node_off[e + 1]))]
+            absent = int(kinds[e]) == _lib.NS_ABSENCE
+            out.append((int(rows[e]),
+                        NMTProof(Start=int(starts[e]), End=int(ends[e]), Nodes=nd[:-1] if absent else nd,
+                                 LeafHash=nd[-1] if absent else None),
+                        [leaves[j].tobytes() for j in range(int(leaf_off[e]), int(leaf_off[e + 1]))]))
+        return out
+
     def SampleProofs(self, coords):
         """Samples of this square with their single-leaf NMT proofs, in one device batch
         (cel_prove_samples: upload, tree index, proofs, download). coords: (row, col, axis)

@@ -499,6 +499,81 @@ cel_status cel_prove_ranges(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32
                             const uint8_t* axes, const uint32_t* index, const int32_t* starts,
                             const int32_t* ends, uint8_t* leaves_out, uint8_t* nodes_out);
 
+/* ------------------------------------------------- namespace queries
+ * nmt ProveNamespace / Proof.VerifyNamespace (nmt v0.22.0 [dep]) in batches: "every share of
+ * namespace N in this square, with a proof that none was left out", what celestia-node's
+ * GetSharesByNamespace asks of every row whose root range holds N.
+ *
+ * The producer works on the row trees of the square whose index is d_index. For namespace nid
+ * and a row of 2k leaves, with lt / le the number of leaves whose namespace is < nid / <= nid:
+ * the row yields an entry iff root.min <= nid <= root.max and lt < 2k. le > lt: an inclusion
+ * entry (CEL_NS_INCLUSION), range [lt, le), the nodes of ProveRange(lt, le), the le - lt shares.
+ * Otherwise an absence entry (CEL_NS_ABSENCE): range [lt, lt + 1), the nodes of ProveRange(lt,
+ * lt + 1) followed by one more 90-byte node, the leaf record of leaf lt (nmt's leafHash), and
+ * no shares. nmt's empty proof for the other rows is not emitted.
+ *
+ * cel_dev_namespace_plan: the entries of n namespaces (host, 29 bytes each, duplicates allowed)
+ * over the 2k rows, in (namespace index, row) order, into the host arrays (cap entries each;
+ * leaf_off / node_off: cap + 1, the prefix sums of the entries' shares and nodes) and *n_entries.
+ * Synchronous on stream: the count depends on the data. cap = 0 with every array NULL: count
+ * only. cap below the count: CEL_EINVAL, both numbers in cel_last_error, *n_entries set, nothing
+ * else written; n * 2k always suffices. The plan stays in d_work
+ * (cel_dev_namespace_workspace_size(k, n) bytes, 16-byte aligned) for cel_dev_namespace_prove.
+ * CEL_EINVAL: nil argument, misalignment, a k that is not a power of two up to 512, the parity
+ * namespace (0xFF * 29, not a data namespace), n * 2k >= 2^32. n = 0 is CEL_OK.
+ * cel_dev_namespace_prove: the first n_entries entries of the plan in d_work: entry e's nodes to
+ * d_nodes + 90 * node_off[e] (2-byte aligned; an absence entry's leaf hash last), its shares to
+ * d_leaves + 512 * leaf_off[e] (16-byte aligned; nullable: nodes only). Asynchronous on stream.
+ * A batch of inclusion entries is byte for byte what cel_dev_prove_batch gives for the same
+ * ranges, so it feeds cel_dev_nmt_verify_batch as well as the namespace verifier below.
+ * cel_namespace_rows: the same for a square in host memory (eds: 2k*2k*512): upload, index
+ * with the order check (an unordered square: CEL_EORDER), plan, proofs, download. Synchronous.
+ * The totals always come back; the arrays are written when cap, leaf_cap (shares) and
+ * node_cap (nodes) suffice, else CEL_EINVAL; all three 0 and every array NULL: count only. */
+#define CEL_NS_INCLUSION 0
+#define CEL_NS_ABSENCE 1
+size_t cel_dev_namespace_workspace_size(uint32_t k, uint32_t n);
+cel_status cel_dev_namespace_plan(cel_ctx* ctx, const void* d_index, uint32_t k, uint32_t n,
+                                  const uint8_t* namespaces, uint64_t cap, uint32_t* ns_idx,
+                                  uint32_t* rows, int32_t* starts, int32_t* ends, uint8_t* kinds,
+                                  uint64_t* leaf_off, uint64_t* node_off, uint64_t* n_entries,
+                                  void* d_work, void* stream);
+cel_status cel_dev_namespace_prove(cel_ctx* ctx, const void* d_eds, const void* d_index, uint32_t k,
+                                   uint64_t n_entries, void* d_leaves, void* d_nodes, void* d_work,
+                                   void* stream);
+cel_status cel_namespace_rows(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32_t n,
+                              const uint8_t* namespaces, uint64_t cap, uint64_t leaf_cap,
+                              uint64_t node_cap, uint32_t* ns_idx, uint32_t* rows, int32_t* starts,
+                              int32_t* ends, uint8_t* kinds, uint64_t* leaf_off, uint64_t* node_off,
+                              uint8_t* leaves_out, uint8_t* nodes_out, uint64_t* n_entries,
+                              uint64_t* total_leaves, uint64_t* total_nodes);
+/* nmt Proof.VerifyNamespace for n proofs: the arguments of cel_nmt_verify_batch and kinds[i]
+ * (CEL_NS_INCLUSION / CEL_NS_ABSENCE; above 1: verdict 0). The leaves are whole 512-byte shares.
+ * Inclusion: as cel_nmt_verify_batch, and every share starts with the namespace. Absence:
+ * end = start + 1, no leaves, at least popcount(start) + 1 nodes, the last of them the leaf
+ * hash, with min <= max and namespace < min, folded as the single leaf. Either kind: every
+ * proof node left of the range ends below the namespace and every node right of it begins
+ * above (completeness). The empty proof (inclusion, start = end, no nodes, no leaves) verifies
+ * iff the namespace lies outside the root's range; any other proof with start = end does not.
+ * Malformed proofs are verdict 0, never an error of the call; CEL_EINVAL as in
+ * cel_nmt_verify_batch. The device form is asynchronous, its workspace
+ * cel_dev_nmt_verify_namespace_workspace_size bytes. */
+cel_status cel_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts,
+                                          const int32_t* ends, const uint8_t* kinds,
+                                          const uint8_t* namespaces, const uint8_t* leaves,
+                                          const uint64_t* leaf_off, const uint8_t* nodes,
+                                          const uint64_t* node_off, const uint8_t* roots,
+                                          uint32_t nroots, const uint32_t* root_idx, uint8_t* ok_out);
+size_t cel_dev_nmt_verify_namespace_workspace_size(uint64_t total_leaves, uint64_t total_nodes,
+                                                   uint32_t n);
+cel_status cel_dev_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts,
+                                              const int32_t* ends, const uint8_t* kinds,
+                                              const uint8_t* namespaces, const void* d_leaves,
+                                              const uint64_t* leaf_off, const void* d_nodes,
+                                              const uint64_t* node_off, const void* d_roots,
+                                              uint32_t nroots, const uint32_t* root_idx, void* d_ok,
+                                              void* d_work, void* stream);
+
 /* Blob share commitments from an EDS (pkg/inclusion).
  * cel_commitment_paths: calculateCommitmentPaths (paths.go:16-47) for a blob of
  * blob_share_len shares placed at the first aligned index >= start of a square of
