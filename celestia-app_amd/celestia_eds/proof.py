@@ -907,56 +907,15 @@ def NewTxInclusionProof(txs, tx_index, max_square_size=128, subtree_root_thresho
 
 
 # ------------------------------------------------------- batched verification
-def VerifyInclusionBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
-    """NMTProof.VerifyInclusion(namespaces[i], leaves_per_proof[i], roots[i]) for every proof
-    in one device batch (cel_nmt_verify_batch): a list of bools. The device verifies the
-    app's sizes: a proof with a node that is not 90 bytes long, a leaf that is not 512, a
-    namespace that is not 29 or a root that is not 90 is False without reaching the device."""
+def _verify_batch(proofs, namespaces, leaves_per_proof, roots, ctx, nodes_of, kind_of):
+    """The batch verifiers' common part: proofs of other sizes than the app's are False, the
+    others flattened into one call. nodes_of(proof): its 90-byte nodes as they travel;
+    kind_of: None for cel_nmt_verify_batch, else proof -> kind for cel_nmt_verify_namespace_batch."""
     n = len(proofs)
     if not (len(namespaces) == len(leaves_per_proof) == len(roots) == n):
         raise CelError(_lib.EINVAL, "proofs, namespaces, leaves and roots differ in number")
     out = [False] * n
     share = _lib.SHARE_SIZE
-    keep = [i for i in range(n)
-            if len(namespaces[i]) == NS and len(roots[i]) == NODE
-            and -(1 << 31) <= proofs[i].Start < 1 << 31 and -(1 << 31) <= proofs[i].End < 1 << 31
-            and all(len(x) == NODE for x in proofs[i].Nodes) and all(len(x) == share for x in leaves_per_proof[i])]
-    if not keep:
-        return out
-    ctx = ctx or _lib.default_context()
-    root_at, root_idx = {}, []
-    for i in keep:
-        root_idx.append(root_at.setdefault(bytes(roots[i]), len(root_at)))
-    leaf_off = np.cumsum([0] + [len(leaves_per_proof[i]) for i in keep]).astype(np.uint64)
-    node_off = np.cumsum([0] + [len(proofs[i].Nodes) for i in keep]).astype(np.uint64)
-    buf = lambda parts: np.frombuffer(b"".join(parts) or b"\0", np.uint8).copy()
-    starts = np.array([proofs[i].Start for i in keep], np.int32)
-    ends = np.array([proofs[i].End for i in keep], np.int32)
-    ns = buf(bytes(namespaces[i]) for i in keep)
-    leaves = buf(bytes(x) for i in keep for x in leaves_per_proof[i])
-    nodes = buf(bytes(x) for i in keep for x in proofs[i].Nodes)
-    rts = buf(root_at)
-    ridx = np.array(root_idx, np.uint32)
-    ok = np.zeros(len(keep), np.uint8)
-    ctx.check(ctx.lib.cel_nmt_verify_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(ns), _p(leaves),
-                                           _p(leaf_off), _p(nodes), _p(node_off), _p(rts), len(root_at), _p(ridx),
-                                           _p(ok)))
-    for i, v in zip(keep, ok):
-        out[i] = bool(v)
-    return out
-
-
-def VerifyNamespaceBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
-    """NMTProof.VerifyNamespace(namespaces[i], leaves_per_proof[i], roots[i]) for every proof in one
-    device batch (cel_nmt_verify_namespace_batch): a list of bools. A proof with a non-empty
-    LeafHash is an absence proof; its leaf hash travels as the last node. Sizes other than the
-    app's are False without reaching the device, as in VerifyInclusionBatch."""
-    n = len(proofs)
-    if not (len(namespaces) == len(leaves_per_proof) == len(roots) == n):
-        raise CelError(_lib.EINVAL, "proofs, namespaces, leaves and roots differ in number")
-    out = [False] * n
-    share = _lib.SHARE_SIZE
-    nodes_of = lambda p: list(p.Nodes) + ([bytes(p.LeafHash)] if p.LeafHash else [])
     keep = [i for i in range(n)
             if len(namespaces[i]) == NS and len(roots[i]) == NODE
             and -(1 << 31) <= proofs[i].Start < 1 << 31 and -(1 << 31) <= proofs[i].End < 1 << 31
@@ -972,19 +931,39 @@ def VerifyNamespaceBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
     buf = lambda parts: np.frombuffer(b"".join(parts) or b"\0", np.uint8).copy()
     starts = np.array([proofs[i].Start for i in keep], np.int32)
     ends = np.array([proofs[i].End for i in keep], np.int32)
-    kinds = np.array([NS_ABSENCE if proofs[i].LeafHash else NS_INCLUSION for i in keep], np.uint8)
     ns = buf(bytes(namespaces[i]) for i in keep)
     leaves = buf(bytes(x) for i in keep for x in leaves_per_proof[i])
     nodes = buf(bytes(x) for i in keep for x in nodes_of(proofs[i]))
     rts = buf(root_at)
     ridx = np.array(root_idx, np.uint32)
     ok = np.zeros(len(keep), np.uint8)
-    ctx.check(ctx.lib.cel_nmt_verify_namespace_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(kinds), _p(ns),
-                                                     _p(leaves), _p(leaf_off), _p(nodes), _p(node_off), _p(rts),
-                                                     len(root_at), _p(ridx), _p(ok)))
+    tail = (_p(ns), _p(leaves), _p(leaf_off), _p(nodes), _p(node_off), _p(rts), len(root_at), _p(ridx), _p(ok))
+    if kind_of is None:
+        ctx.check(ctx.lib.cel_nmt_verify_batch(ctx.handle, len(keep), _p(starts), _p(ends), *tail))
+    else:
+        kinds = np.array([kind_of(proofs[i]) for i in keep], np.uint8)
+        ctx.check(ctx.lib.cel_nmt_verify_namespace_batch(ctx.handle, len(keep), _p(starts), _p(ends), _p(kinds), *tail))
     for i, v in zip(keep, ok):
         out[i] = bool(v)
     return out
+
+
+def VerifyInclusionBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
+    """NMTProof.VerifyInclusion(namespaces[i], leaves_per_proof[i], roots[i]) for every proof
+    in one device batch (cel_nmt_verify_batch): a list of bools. The device verifies the
+    app's sizes: a proof with a node that is not 90 bytes long, a leaf that is not 512, a
+    namespace that is not 29 or a root that is not 90 is False without reaching the device."""
+    return _verify_batch(proofs, namespaces, leaves_per_proof, roots, ctx, lambda p: p.Nodes, None)
+
+
+def VerifyNamespaceBatch(proofs, namespaces, leaves_per_proof, roots, ctx=None):
+    """NMTProof.VerifyNamespace(namespaces[i], leaves_per_proof[i], roots[i]) for every proof in one
+    device batch (cel_nmt_verify_namespace_batch): a list of bools. A proof with a non-empty
+    LeafHash is an absence proof; its leaf hash travels as the last node. Sizes other than the
+    app's are False without reaching the device, as in VerifyInclusionBatch."""
+    return _verify_batch(proofs, namespaces, leaves_per_proof, roots, ctx,
+                         lambda p: list(p.Nodes) + ([bytes(p.LeafHash)] if p.LeafHash else []),
+                         lambda p: NS_ABSENCE if p.LeafHash else NS_INCLUSION)
 
 
 def VerifyShareProofs(share_proofs, root, ctx=None):

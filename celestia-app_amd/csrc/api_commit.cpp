@@ -55,13 +55,6 @@ cel_status commit_check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t sh
 cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const uint64_t* offs,
                           const CommitItem* items, uint32_t nb, uint32_t threshold, uint8_t* d_out, void* d_work,
                           hipStream_t s) {
-  hipError_t e;
-  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  if (ctx->plan_pending) {
-    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) return hip_fail(ctx, e, "plan upload");
-    ctx->plan_pending = false;
-  }
   blob::Plan plan;
   plan.recs.reserve(nb);
   uint64_t off = base_off;
@@ -75,23 +68,15 @@ cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off
   // the head of blob_work's layout (blob_commit.hip): the records, then the slot table
   const size_t rec_bytes = align256((size_t)nb * sizeof(blob::Rec));
   const size_t bytes = rec_bytes + slots * 4;
-  if (ctx->plan_stage_size < bytes) {
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
-    ctx->plan_stage = nullptr;
-    ctx->plan_stage_size = 0;
-    if (hipHostMalloc(&ctx->plan_stage, bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->plan_stage = nullptr;
-      return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-    }
-    ctx->plan_stage_size = bytes;
-  }
-  uint8_t* st = static_cast<uint8_t*>(ctx->plan_stage);
+  cel_status status = CEL_OK;
+  uint8_t* st = static_cast<uint8_t*>(plan_stage(ctx, bytes, &status));
+  if (!st) return status;
   std::memset(st, 0, rec_bytes);
   std::memcpy(st, plan.recs.data(), (size_t)nb * sizeof(blob::Rec));
   blob::plan_finish(plan, reinterpret_cast<uint32_t*>(st + rec_bytes));
+  hipError_t e;
   if ((e = hipMemcpyAsync(d_work, st, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
-  if ((e = hipEventRecord(ctx->ev_plan, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->plan_pending = true;
+  if ((status = plan_uploaded(ctx, s)) != CEL_OK) return status;
   // Measurement aid (tools/commit_bench.py --leaf-ab): CEL_COMMIT_LEAF=expanded runs the leaf
   // stage's A/B partner, which first writes every share into ctx scratch (512 B per slot).
   uint32_t* d_shares = nullptr;

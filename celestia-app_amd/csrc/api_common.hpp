@@ -50,6 +50,46 @@ inline void* host_stage(cel_ctx* ctx, size_t bytes) {
   return ctx->hstage;
 }
 
+// The ctx's page-locked plan buffer with room for `bytes`, once its last upload has left it
+// (the ev_plan rule of cel_internal.hpp). nullptr with the status in *st. A caller that
+// uploads from the buffer calls plan_uploaded behind the copy, unless it waits for the stream
+// itself before it returns (the namespace plan).
+inline void* plan_stage(cel_ctx* ctx, size_t bytes, cel_status* st) {
+  if (bytes == 0) bytes = 256;  // never nullptr on success
+  hipError_t e;
+  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess) {
+    *st = hip_fail(ctx, e, "event");
+    return nullptr;
+  }
+  if (ctx->plan_pending) {
+    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) {
+      *st = hip_fail(ctx, e, "plan upload");
+      return nullptr;
+    }
+    ctx->plan_pending = false;
+  }
+  if (ctx->plan_stage_size < bytes) {
+    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
+    ctx->plan_stage = nullptr;
+    ctx->plan_stage_size = 0;
+    if (hipHostMalloc(&ctx->plan_stage, bytes, hipHostMallocDefault) != hipSuccess) {
+      ctx->plan_stage = nullptr;
+      *st = fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
+      return nullptr;
+    }
+    ctx->plan_stage_size = bytes;
+  }
+  return ctx->plan_stage;
+}
+
+// After the copy out of the plan buffer has been enqueued on s: the next plan_stage waits for it.
+inline cel_status plan_uploaded(cel_ctx* ctx, hipStream_t s) {
+  const hipError_t e = hipEventRecord(ctx->ev_plan, s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "event");
+  ctx->plan_pending = true;
+  return CEL_OK;
+}
+
 inline bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
 
 // da.SquareSize: RoundUpPowerOfTwo(ceil(sqrt(len))) (data_availability_header.go:205-215)

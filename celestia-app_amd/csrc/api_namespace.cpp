@@ -3,10 +3,9 @@
 //       (namespace, row) of a batch over one resident square: what celestia-node's
 //       GetSharesByNamespace asks of every row whose root range holds the namespace
 //   cel_namespace_rows                                 the same for a square in host memory
-//   cel_nmt_verify_namespace_batch / cel_dev_...       <- nmt Proof.VerifyNamespace [dep]
 // The plan's sizes depend on the data, so the device finds, counts and places the entries
-// (nmt_namespace.hip) and the plan call waits for the counts; the verifier's host side is the
-// inclusion verifier's (api_verify.cpp) with the proofs' kinds.
+// (nmt_namespace.hip) and the plan call waits for the counts. The verifier of these proofs
+// (cel_nmt_verify_namespace_batch) is in api_verify.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -17,7 +16,6 @@
 #include "api_common.hpp"
 #include "cel_internal.hpp"
 #include "nmt_namespace.hpp"
-#include "nmt_verify.hpp"
 
 using namespace cel;
 using namespace cel::abi;
@@ -25,35 +23,6 @@ using namespace cel::abi;
 namespace {
 
 bool plan_width(uint32_t k) { return is_pow2(k) && k <= 512; }
-
-// The ctx's page-locked plan buffer with room for `bytes`, once its last upload has left it
-// (the ev_plan rule of cel_internal.hpp). nullptr with the status in *st.
-void* plan_stage(cel_ctx* ctx, size_t bytes, cel_status* st) {
-  hipError_t e;
-  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess) {
-    *st = hip_fail(ctx, e, "event");
-    return nullptr;
-  }
-  if (ctx->plan_pending) {
-    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) {
-      *st = hip_fail(ctx, e, "plan upload");
-      return nullptr;
-    }
-    ctx->plan_pending = false;
-  }
-  if (ctx->plan_stage_size < bytes) {
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
-    ctx->plan_stage = nullptr;
-    ctx->plan_stage_size = 0;
-    if (hipHostMalloc(&ctx->plan_stage, bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->plan_stage = nullptr;
-      *st = fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-      return nullptr;
-    }
-    ctx->plan_stage_size = bytes;
-  }
-  return ctx->plan_stage;
-}
 
 // "" if the n namespaces can be planned over a square of width k, else what is wrong.
 std::string plan_error(uint32_t k, uint32_t n, const uint8_t* namespaces) {
@@ -91,6 +60,7 @@ cel_status plan_locked(cel_ctx* ctx, const void* d_index, uint32_t k, uint32_t n
     stage[(size_t)i * 32 + 29] = stage[(size_t)i * 32 + 30] = stage[(size_t)i * 32 + 31] = 0;
   }
   hipError_t e;
+  // no plan_uploaded behind this copy: the call waits for s below, before anyone refills the buffer
   if ((e = hipMemcpyAsync(w.ns, stage, ns_b, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
   // Measurement aid (tools/namespace_bench.py): CEL_NS_PLAN_STAGES = a mask of the stages to run
   // (1 find, 2 prefix sum and compaction) over what the others left in the workspace.
@@ -108,7 +78,7 @@ cel_status plan_locked(cel_ctx* ctx, const void* d_index, uint32_t k, uint32_t n
     return fail(ctx, CEL_EINVAL, "cap " + std::to_string(out.cap) + " is below the " + std::to_string(tot->entries) +
                                      " entries of the plan");
   const size_t req_b = (size_t)tot->entries * sizeof(nsq::Request);
-  nsq::Request* req = static_cast<nsq::Request*>(plan_stage(ctx, req_b ? req_b : 1, &st));
+  nsq::Request* req = static_cast<nsq::Request*>(plan_stage(ctx, req_b, &st));
   if (!req) return st;
   if (req_b) {
     if ((e = hipMemcpyAsync(req, w.req, req_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
@@ -127,85 +97,6 @@ cel_status plan_locked(cel_ctx* ctx, const void* d_index, uint32_t k, uint32_t n
   out.leaf_off[tot->entries] = tot->leaves;
   out.node_off[tot->entries] = tot->nodes;
   return CEL_OK;
-}
-
-// ------------------------------------------------------------------ the verifier's host side
-
-constexpr uint64_t kMaxRecords = 1ull << 31;  // leaves, nodes: record indices fit 32 bits with room
-
-struct Batch {
-  uint32_t n;
-  const int32_t *starts, *ends;
-  const uint8_t* kinds;
-  const uint8_t* namespaces;
-  const uint64_t *leaf_off, *node_off;
-  uint32_t nroots;
-  const uint32_t* root_idx;
-  uint64_t total_leaves() const { return leaf_off[n] - leaf_off[0]; }
-  uint64_t total_nodes() const { return node_off[n] - node_off[0]; }
-};
-
-cel_status check_batch(cel_ctx* ctx, const Batch& b) {
-  for (uint32_t i = 0; i < b.n; i++) {
-    if (b.leaf_off[i + 1] < b.leaf_off[i]) return fail(ctx, CEL_EINVAL, "leaf offsets must be non-decreasing");
-    if (b.node_off[i + 1] < b.node_off[i]) return fail(ctx, CEL_EINVAL, "node offsets must be non-decreasing");
-    if (b.root_idx[i] >= b.nroots)
-      return fail(ctx, CEL_EINVAL, "proof " + std::to_string(i) + ": root index " + std::to_string(b.root_idx[i]) +
-                                       " of " + std::to_string(b.nroots) + " roots");
-  }
-  if (b.total_leaves() + b.n >= kMaxRecords || b.total_nodes() + b.n >= kMaxRecords)
-    return fail(ctx, CEL_ETOOBIG, "too many leaves or nodes for one device batch");
-  return CEL_OK;
-}
-
-// verify_enqueue of api_verify.cpp with the proofs' kinds in the table.
-cel_status verify_enqueue(cel_ctx* ctx, const Batch& b, const uint8_t* d_leaves, const uint8_t* d_nodes,
-                          const uint8_t* d_roots, uint8_t* d_ok, void* d_work, hipStream_t s) {
-  const uint64_t tl = b.total_leaves(), tn = b.total_nodes();
-  const VerifyNsWork dev = verify_ns_carve(d_work, tl, tn, b.n);
-  cel_status st = CEL_OK;
-  void* stage = plan_stage(ctx, dev.v.head_bytes, &st);
-  if (!stage) return st;
-  const VerifyWork host = verify_carve(stage, tl + b.n, tn, b.n);
-  for (uint32_t i = 0; i < b.n; i++) {
-    VerifyProof& p = host.proofs[i];
-    p.start = b.starts[i];
-    p.end = b.ends[i];
-    const uint64_t nl = b.leaf_off[i + 1] - b.leaf_off[i], nn = b.node_off[i + 1] - b.node_off[i];
-    p.nleaves = (uint32_t)nl;
-    p.nnodes = (uint32_t)nn;
-    p.leaf0 = b.leaf_off[i] - b.leaf_off[0];
-    p.node0 = b.node_off[i] - b.node_off[0];
-    p.root = b.root_idx[i];
-    p.pad = b.kinds[i];
-    uint8_t* ns = reinterpret_cast<uint8_t*>(host.ns) + (size_t)i * 32;
-    std::memcpy(ns, b.namespaces + (size_t)i * kNs, kNs);
-    ns[29] = ns[30] = ns[31] = 0;
-    for (uint64_t j = 0; j < nl; j++) host.leaf_proof[p.leaf0 + j] = i;
-  }
-  hipError_t e;
-  if ((e = hipMemcpyAsync(d_work, stage, dev.v.head_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
-    return hip_fail(ctx, e, "H2D");
-  if ((e = hipEventRecord(ctx->ev_plan, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->plan_pending = true;
-  // Measurement aid (tools/namespace_bench.py): CEL_VERIFY_STAGES as in api_verify.cpp.
-  int stages = kVerifyAll;
-  if (const char* env = std::getenv("CEL_VERIFY_STAGES")) stages = std::atoi(env) & kVerifyAll;
-  Range r("nmt_verify_namespace");
-  if ((e = launch_verify_ns(dev, d_leaves, tl, d_nodes, tn, d_roots, b.n, d_ok, stages, s)) != hipSuccess)
-    return hip_fail(ctx, e, "nmt verify namespace");
-  return CEL_OK;
-}
-
-cel_status upload(cel_ctx* ctx, void* dst, const void* src, size_t bytes, uint8_t* stage, size_t* at, hipStream_t s) {
-  if (!bytes) return CEL_OK;
-  if (!page_locked(src)) {
-    std::memcpy(stage + *at, src, bytes);
-    src = stage + *at;
-    *at += align256(bytes);
-  }
-  const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s);
-  return e == hipSuccess ? CEL_OK : hip_fail(ctx, e, "H2D");
 }
 
 }  // namespace
@@ -333,71 +224,6 @@ cel_status cel_namespace_rows(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint
   if (node_b && (e = hipMemcpyAsync(nodes_out, d_nodes, node_b, hipMemcpyDeviceToHost, s)) != hipSuccess)
     return hip_fail(ctx, e, "D2H");
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  return CEL_OK;
-}
-
-size_t cel_dev_nmt_verify_namespace_workspace_size(uint64_t total_leaves, uint64_t total_nodes, uint32_t n) {
-  return verify_ns_carve(nullptr, total_leaves, total_nodes, n).bytes;
-}
-
-cel_status cel_dev_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
-                                              const uint8_t* kinds, const uint8_t* namespaces, const void* d_leaves,
-                                              const uint64_t* leaf_off, const void* d_nodes, const uint64_t* node_off,
-                                              const void* d_roots, uint32_t nroots, const uint32_t* root_idx,
-                                              void* d_ok, void* d_work, void* stream) {
-  if (!ctx) return CEL_EINVAL;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (n == 0) return CEL_OK;
-  if (!starts || !ends || !kinds || !namespaces || !d_leaves || !leaf_off || !d_nodes || !node_off || !d_roots ||
-      !root_idx || !d_ok || !d_work)
-    return fail(ctx, CEL_EINVAL, "nil argument");
-  if (reinterpret_cast<uintptr_t>(d_leaves) & 15) return fail(ctx, CEL_EINVAL, "d_leaves must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(d_work) & 15) return fail(ctx, CEL_EINVAL, "d_work must be 16-byte aligned");
-  const Batch b{n, starts, ends, kinds, namespaces, leaf_off, node_off, nroots, root_idx};
-  cel_status st = check_batch(ctx, b);
-  if (st) return st;
-  DeviceGuard g(ctx->device);
-  return verify_enqueue(ctx, b, static_cast<const uint8_t*>(d_leaves) + leaf_off[0] * kShare,
-                        static_cast<const uint8_t*>(d_nodes) + node_off[0] * kNode, static_cast<const uint8_t*>(d_roots),
-                        static_cast<uint8_t*>(d_ok), d_work, pick_stream(ctx, stream));
-}
-
-cel_status cel_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
-                                          const uint8_t* kinds, const uint8_t* namespaces, const uint8_t* leaves,
-                                          const uint64_t* leaf_off, const uint8_t* nodes, const uint64_t* node_off,
-                                          const uint8_t* roots, uint32_t nroots, const uint32_t* root_idx,
-                                          uint8_t* ok_out) {
-  if (!ctx) return CEL_EINVAL;
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  if (n == 0) return CEL_OK;
-  if (!starts || !ends || !kinds || !namespaces || !leaves || !leaf_off || !nodes || !node_off || !roots || !root_idx ||
-      !ok_out)
-    return fail(ctx, CEL_EINVAL, "nil argument");
-  const Batch b{n, starts, ends, kinds, namespaces, leaf_off, node_off, nroots, root_idx};
-  cel_status st = check_batch(ctx, b);
-  if (st) return st;
-  DeviceGuard g(ctx->device);
-  hipStream_t s = ctx->stream;
-  const uint64_t tl = b.total_leaves(), tn = b.total_nodes();
-  const size_t leaf_b = (size_t)tl * kShare, node_b = (size_t)tn * kNode, root_b = (size_t)nroots * kNode;
-  const size_t ok_a = align256(n);
-  hipError_t e = hipSuccess;
-  uint8_t* d_leaves = static_cast<uint8_t*>(scratch(ctx, S_IN, leaf_b, &e));
-  uint8_t* d_nodes = static_cast<uint8_t*>(scratch(ctx, S_AUX, align256(node_b) + root_b, &e));
-  void* d_work = scratch(ctx, S_WORK, verify_ns_carve(nullptr, tl, tn, n).bytes, &e);
-  uint8_t* d_ok = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, ok_a, &e));
-  if (!d_leaves || !d_nodes || !d_work || !d_ok) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  uint8_t* d_roots = d_nodes + align256(node_b);
-  uint8_t* hs = static_cast<uint8_t*>(host_stage(ctx, ok_a + align256(leaf_b) + align256(node_b) + align256(root_b)));
-  if (!hs) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  size_t at = ok_a;
-  if ((st = upload(ctx, d_leaves, leaves + leaf_off[0] * kShare, leaf_b, hs, &at, s)) != CEL_OK) return st;
-  if ((st = upload(ctx, d_nodes, nodes + node_off[0] * kNode, node_b, hs, &at, s)) != CEL_OK) return st;
-  if ((st = upload(ctx, d_roots, roots, root_b, hs, &at, s)) != CEL_OK) return st;
-  if ((st = verify_enqueue(ctx, b, d_leaves, d_nodes, d_roots, d_ok, d_work, s)) != CEL_OK) return st;
-  if ((e = hipMemcpyAsync(hs, d_ok, n, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  std::memcpy(ok_out, hs, n);
   return CEL_OK;
 }
 

@@ -53,27 +53,12 @@ cel_status prove_enqueue(cel_ctx* ctx, const uint8_t* d_eds, const void* d_index
                          const uint8_t* axes, const uint32_t* index, const int32_t* starts, const int32_t* ends,
                          uint8_t* d_leaves, uint8_t* d_nodes, void* d_work, hipStream_t s) {
   const prove::IndexLayout x = prove::index_layout(k);
-  hipError_t e;
-  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  if (ctx->plan_pending) {
-    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) return hip_fail(ctx, e, "plan upload");
-    ctx->plan_pending = false;
-  }
   const size_t bytes = (size_t)n * sizeof(prove::Request);
-  if (ctx->plan_stage_size < bytes) {
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
-    ctx->plan_stage = nullptr;
-    ctx->plan_stage_size = 0;
-    if (hipHostMalloc(&ctx->plan_stage, bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->plan_stage = nullptr;
-      return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-    }
-    ctx->plan_stage_size = bytes;
-  }
+  cel_status st = CEL_OK;
+  prove::Request* req = static_cast<prove::Request*>(plan_stage(ctx, bytes, &st));
+  if (!req) return st;
   // one pass: each request checked and written with the running sums of cel_prove_offsets;
   // nothing is enqueued before the last one has passed
-  prove::Request* req = static_cast<prove::Request*>(ctx->plan_stage);
   uint64_t node0 = 0, leaf0 = 0;
   for (uint32_t i = 0; i < n; i++) {
     if (axes[i] > 1) return fail(ctx, CEL_EINVAL, "proof " + std::to_string(i) + ": axis " + std::to_string(axes[i]));
@@ -86,9 +71,9 @@ cel_status prove_enqueue(cel_ctx* ctx, const uint8_t* d_eds, const void* d_index
     leaf0 += (uint64_t)(ends[i] - starts[i]);
     node0 += prove::node_count(x.L, (uint32_t)starts[i], (uint32_t)ends[i] - 1);
   }
+  hipError_t e;
   if ((e = hipMemcpyAsync(d_work, req, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
-  if ((e = hipEventRecord(ctx->ev_plan, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->plan_pending = true;
+  if ((st = plan_uploaded(ctx, s)) != CEL_OK) return st;
   if ((e = launch_prove(d_eds, d_index, k, static_cast<const prove::Request*>(d_work), n, d_leaves, d_nodes, s)) !=
       hipSuccess)
     return hip_fail(ctx, e, "nmt prove");

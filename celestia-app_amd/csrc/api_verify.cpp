@@ -1,4 +1,4 @@
-// C ABI of the batched NMT proof verifier and of the repair from proven samples
+// C ABI of the batched NMT proof verifiers and of the repair from proven samples
 // (include/celestia_eds.h):
 //   cel_nmt_verify_batch / cel_dev_nmt_verify_batch  <- nmt Proof.VerifyInclusion (nmt v0.22.0
 //       proof.go [dep]) for every proof of a batch: the NMT range proofs of ShareProofs
@@ -6,6 +6,8 @@
 //   cel_dev_place_samples  <- cells with single-leaf proofs against the DAH's row or column
 //       roots, checked and then written into a resident EDS
 //   cel_repair_samples     <- the same into an empty square, then cel_dev_repair
+//   cel_nmt_verify_namespace_batch / cel_dev_nmt_verify_namespace_batch  <- nmt
+//       Proof.VerifyNamespace [dep]: the same host side with the proofs' kinds in the table
 // The host flattens the proofs into a table (nmt_verify.hpp) and picks the sample that
 // fills each cell; every hash runs in nmt_verify.hip.
 #include <hip/hip_runtime.h>
@@ -26,13 +28,17 @@ namespace {
 
 constexpr uint64_t kMaxRecords = 1ull << 31;  // leaves, nodes: record indices fit 32 bits with room
 
+// A batch of proofs under one of the two rules: kinds == nullptr is VerifyInclusion, else
+// VerifyNamespace with kinds[i] the kind of proof i (CEL_NS_INCLUSION / CEL_NS_ABSENCE).
 struct Batch {
   uint32_t n;
   const int32_t *starts, *ends;
+  const uint8_t* kinds;
   const uint8_t* namespaces;
   const uint64_t *leaf_off, *node_off;
   uint32_t nroots;
   const uint32_t* root_idx;
+  bool by_namespace() const { return kinds != nullptr; }
   uint64_t total_leaves() const { return leaf_off[n] - leaf_off[0]; }
   uint64_t total_nodes() const { return node_off[n] - node_off[0]; }
 };
@@ -46,36 +52,28 @@ cel_status check_batch(cel_ctx* ctx, const Batch& b) {
       return fail(ctx, CEL_EINVAL, "proof " + std::to_string(i) + ": root index " + std::to_string(b.root_idx[i]) +
                                        " of " + std::to_string(b.nroots) + " roots");
   }
-  if (b.total_leaves() >= kMaxRecords || b.total_nodes() + b.n >= kMaxRecords)
+  // the namespace rule keeps one more leaf record per proof (verify_ns_carve), the node
+  // records one root per proof under both rules
+  const uint64_t own_records = b.by_namespace() ? b.n : 0;
+  if (b.total_leaves() + own_records >= kMaxRecords || b.total_nodes() + b.n >= kMaxRecords)
     return fail(ctx, CEL_ETOOBIG, "too many leaves or nodes for one device batch");
   return CEL_OK;
 }
 
-// Fills the table of batch b in the ctx's page-locked plan buffer (under its ev_plan rule, as
-// the blob commitments do), uploads it into d_work's head and enqueues the kernels on s.
-// d_leaves / d_nodes: the first leaf / node of the batch. ctx->mu held, device current.
+// Fills the table of batch b in the ctx's page-locked plan buffer (api_common.hpp: plan_stage),
+// uploads it into d_work's head and enqueues the kernels of b's rule on s. d_leaves / d_nodes:
+// the first leaf / node of the batch. ctx->mu held, device current.
 cel_status verify_enqueue(cel_ctx* ctx, const Batch& b, const uint8_t* d_leaves, const uint8_t* d_nodes,
                           const uint8_t* d_roots, uint8_t* d_ok, void* d_work, hipStream_t s) {
-  hipError_t e;
-  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  if (ctx->plan_pending) {
-    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) return hip_fail(ctx, e, "plan upload");
-    ctx->plan_pending = false;
-  }
   const uint64_t tl = b.total_leaves(), tn = b.total_nodes();
-  const VerifyWork dev = verify_carve(d_work, tl, tn, b.n);
-  if (ctx->plan_stage_size < dev.head_bytes) {
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
-    ctx->plan_stage = nullptr;
-    ctx->plan_stage_size = 0;
-    if (hipHostMalloc(&ctx->plan_stage, dev.head_bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->plan_stage = nullptr;
-      return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-    }
-    ctx->plan_stage_size = dev.head_bytes;
-  }
-  const VerifyWork host = verify_carve(ctx->plan_stage, tl, tn, b.n);
+  // the table is the same under both rules; the namespace rule's workspace has more behind it
+  VerifyNsWork ns_dev{};
+  if (b.by_namespace()) ns_dev = verify_ns_carve(d_work, tl, tn, b.n);
+  const VerifyWork dev = b.by_namespace() ? ns_dev.v : verify_carve(d_work, tl, tn, b.n);
+  cel_status st = CEL_OK;
+  void* stage = plan_stage(ctx, dev.head_bytes, &st);
+  if (!stage) return st;
+  const VerifyWork host = b.by_namespace() ? verify_ns_carve(stage, tl, tn, b.n).v : verify_carve(stage, tl, tn, b.n);
   for (uint32_t i = 0; i < b.n; i++) {
     VerifyProof& p = host.proofs[i];
     p.start = b.starts[i];
@@ -86,24 +84,30 @@ cel_status verify_enqueue(cel_ctx* ctx, const Batch& b, const uint8_t* d_leaves,
     p.leaf0 = b.leaf_off[i] - b.leaf_off[0];
     p.node0 = b.node_off[i] - b.node_off[0];
     p.root = b.root_idx[i];
-    p.pad = 0;
+    p.pad = b.by_namespace() ? b.kinds[i] : 0;
     uint8_t* ns = reinterpret_cast<uint8_t*>(host.ns) + (size_t)i * 32;
     std::memcpy(ns, b.namespaces + (size_t)i * kNs, kNs);
     ns[29] = ns[30] = ns[31] = 0;
     for (uint64_t j = 0; j < nl; j++) host.leaf_proof[p.leaf0 + j] = i;
   }
-  if ((e = hipMemcpyAsync(d_work, ctx->plan_stage, dev.head_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+  hipError_t e;
+  if ((e = hipMemcpyAsync(d_work, stage, dev.head_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
     return hip_fail(ctx, e, "H2D");
-  if ((e = hipEventRecord(ctx->ev_plan, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->plan_pending = true;
-  // Measurement aid (tools/verify_bench.py): CEL_VERIFY_STAGES = a mask of the stages to run
-  // (1 repack, 2 leaves, 4 fold), so that one stage can be timed over the records the
-  // others left in the workspace.
+  if ((st = plan_uploaded(ctx, s)) != CEL_OK) return st;
+  // Measurement aid (tools/verify_bench.py, tools/namespace_bench.py): CEL_VERIFY_STAGES = a
+  // mask of the stages to run (1 repack, 2 leaves, 4 fold), so that one stage can be timed
+  // over the records the others left in the workspace.
   int stages = kVerifyAll;
   if (const char* env = std::getenv("CEL_VERIFY_STAGES")) stages = std::atoi(env) & kVerifyAll;
-  Range r("nmt_verify");
-  if ((e = launch_verify(dev, d_leaves, tl, d_nodes, tn, d_roots, b.n, d_ok, stages, s)) != hipSuccess)
-    return hip_fail(ctx, e, "nmt verify");
+  if (b.by_namespace()) {
+    Range r("nmt_verify_namespace");
+    if ((e = launch_verify_ns(ns_dev, d_leaves, tl, d_nodes, tn, d_roots, b.n, d_ok, stages, s)) != hipSuccess)
+      return hip_fail(ctx, e, "nmt verify namespace");
+  } else {
+    Range r("nmt_verify");
+    if ((e = launch_verify(dev, d_leaves, tl, d_nodes, tn, d_roots, b.n, d_ok, stages, s)) != hipSuccess)
+      return hip_fail(ctx, e, "nmt verify");
+  }
   return CEL_OK;
 }
 
@@ -134,7 +138,9 @@ cel_status verify_host(cel_ctx* ctx, const Batch& b, const uint8_t* leaves, cons
   hipError_t e = hipSuccess;
   uint8_t* d_leaves = static_cast<uint8_t*>(scratch(ctx, S_IN, leaf_b, &e));
   uint8_t* d_nodes = static_cast<uint8_t*>(scratch(ctx, S_AUX, align256(node_b) + root_b, &e));
-  void* d_work = scratch(ctx, S_WORK, verify_carve(nullptr, tl, tn, b.n).bytes, &e);
+  const size_t work_b = b.by_namespace() ? verify_ns_carve(nullptr, tl, tn, b.n).bytes
+                                         : verify_carve(nullptr, tl, tn, b.n).bytes;
+  void* d_work = scratch(ctx, S_WORK, work_b, &e);
   uint8_t* d_ok = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, ok_a + extra, &e));
   if (!d_leaves || !d_nodes || !d_work || !d_ok) return fail(ctx, CEL_ENOMEM, "device allocation failed");
   uint8_t* d_roots = d_nodes + align256(node_b);
@@ -187,7 +193,7 @@ cel_status place_samples_locked(cel_ctx* ctx, uint8_t* d_eds, uint8_t* present, 
       std::memset(&ns[(size_t)i * kNs], 0xFF, kNs);
   }
   leaf_off[n] = n;
-  const Batch b{n, starts.data(), ends.data(), ns.data(), leaf_off.data(), node_off, 2 * W, root_idx.data()};
+  const Batch b{n, starts.data(), ends.data(), nullptr, ns.data(), leaf_off.data(), node_off, 2 * W, root_idx.data()};
   uint8_t *d_shares = nullptr, *d_lists = nullptr;
   cel_status st = verify_host(ctx, b, shares, nodes, roots.data(), ok_out, (size_t)n * 8, &d_shares, &d_lists);
   if (st) return st;
@@ -235,7 +241,7 @@ cel_status cel_nmt_verify_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts,
   if (!starts || !ends || !namespaces || !leaves || !leaf_off || !nodes || !node_off || !roots || !root_idx || !ok_out)
     return fail(ctx, CEL_EINVAL, "nil argument");
   DeviceGuard g(ctx->device);
-  const Batch b{n, starts, ends, namespaces, leaf_off, node_off, nroots, root_idx};
+  const Batch b{n, starts, ends, nullptr, namespaces, leaf_off, node_off, nroots, root_idx};
   return verify_host(ctx, b, leaves, nodes, roots, ok_out, 0, nullptr, nullptr);
 }
 
@@ -255,7 +261,7 @@ cel_status cel_dev_nmt_verify_batch(cel_ctx* ctx, uint32_t n, const int32_t* sta
       !d_ok || !d_work)
     return fail(ctx, CEL_EINVAL, "nil argument");
   if (reinterpret_cast<uintptr_t>(d_leaves) & 15) return fail(ctx, CEL_EINVAL, "d_leaves must be 16-byte aligned");
-  const Batch b{n, starts, ends, namespaces, leaf_off, node_off, nroots, root_idx};
+  const Batch b{n, starts, ends, nullptr, namespaces, leaf_off, node_off, nroots, root_idx};
   cel_status st = check_batch(ctx, b);
   if (st) return st;
   DeviceGuard g(ctx->device);
@@ -263,6 +269,48 @@ cel_status cel_dev_nmt_verify_batch(cel_ctx* ctx, uint32_t n, const int32_t* sta
                         static_cast<const uint8_t*>(d_nodes) + node_off[0] * kNode,
                         static_cast<const uint8_t*>(d_roots), static_cast<uint8_t*>(d_ok), d_work,
                         pick_stream(ctx, stream));
+}
+
+size_t cel_dev_nmt_verify_namespace_workspace_size(uint64_t total_leaves, uint64_t total_nodes, uint32_t n) {
+  return verify_ns_carve(nullptr, total_leaves, total_nodes, n).bytes;
+}
+
+cel_status cel_dev_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
+                                              const uint8_t* kinds, const uint8_t* namespaces, const void* d_leaves,
+                                              const uint64_t* leaf_off, const void* d_nodes, const uint64_t* node_off,
+                                              const void* d_roots, uint32_t nroots, const uint32_t* root_idx,
+                                              void* d_ok, void* d_work, void* stream) {
+  if (!ctx) return CEL_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (n == 0) return CEL_OK;
+  if (!starts || !ends || !kinds || !namespaces || !d_leaves || !leaf_off || !d_nodes || !node_off || !d_roots ||
+      !root_idx || !d_ok || !d_work)
+    return fail(ctx, CEL_EINVAL, "nil argument");
+  if (reinterpret_cast<uintptr_t>(d_leaves) & 15) return fail(ctx, CEL_EINVAL, "d_leaves must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(d_work) & 15) return fail(ctx, CEL_EINVAL, "d_work must be 16-byte aligned");
+  const Batch b{n, starts, ends, kinds, namespaces, leaf_off, node_off, nroots, root_idx};
+  cel_status st = check_batch(ctx, b);
+  if (st) return st;
+  DeviceGuard g(ctx->device);
+  return verify_enqueue(ctx, b, static_cast<const uint8_t*>(d_leaves) + leaf_off[0] * kShare,
+                        static_cast<const uint8_t*>(d_nodes) + node_off[0] * kNode, static_cast<const uint8_t*>(d_roots),
+                        static_cast<uint8_t*>(d_ok), d_work, pick_stream(ctx, stream));
+}
+
+cel_status cel_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const int32_t* starts, const int32_t* ends,
+                                          const uint8_t* kinds, const uint8_t* namespaces, const uint8_t* leaves,
+                                          const uint64_t* leaf_off, const uint8_t* nodes, const uint64_t* node_off,
+                                          const uint8_t* roots, uint32_t nroots, const uint32_t* root_idx,
+                                          uint8_t* ok_out) {
+  if (!ctx) return CEL_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (n == 0) return CEL_OK;
+  if (!starts || !ends || !kinds || !namespaces || !leaves || !leaf_off || !nodes || !node_off || !roots || !root_idx ||
+      !ok_out)
+    return fail(ctx, CEL_EINVAL, "nil argument");
+  DeviceGuard g(ctx->device);
+  const Batch b{n, starts, ends, kinds, namespaces, leaf_off, node_off, nroots, root_idx};
+  return verify_host(ctx, b, leaves, nodes, roots, ok_out, 0, nullptr, nullptr);
 }
 
 cel_status cel_dev_place_samples(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t k, const uint8_t* row_roots,

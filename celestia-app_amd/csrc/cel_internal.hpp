@@ -303,10 +303,15 @@ struct cel_ctx {
   // Grow-only page-locked host staging (the repair's axis lists).
   void* hstage = nullptr;
   size_t hstage_size = 0;
-  // Page-locked plan tables of the blob commitment calls (api_commit.cpp) and proof tables of
-  // the NMT verifier (api_verify.cpp). The asynchronous entry returns while their upload may
-  // still be queued, so they have a buffer of their own and the next call waits for ev_plan
-  // (recorded after the upload) before refilling it.
+  // Page-locked tables on their way to the device: the plans of the blob commitment calls
+  // (api_commit.cpp), the proof tables of the NMT verifiers (api_verify.cpp), the request
+  // table of the prover (api_prove.cpp) and the namespaces of a namespace plan
+  // (api_namespace.cpp). The asynchronous entry returns while the upload may still be queued,
+  // so the tables have a buffer of their own and the next call waits for ev_plan (recorded
+  // after the upload) before refilling it. plan_stage and plan_uploaded (api_common.hpp) are
+  // that rule, and but for the ctx's teardown nothing else touches these four fields. A caller
+  // may build its table before it asks for the buffer, as commit_enqueue does: nothing in
+  // between touches the buffer, so the wait may come after the planning.
   void* plan_stage = nullptr;
   size_t plan_stage_size = 0;
   hipEvent_t ev_plan = nullptr;

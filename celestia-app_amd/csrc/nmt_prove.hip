@@ -32,9 +32,6 @@ namespace cel {
 
 using prove::Request;
 
-constexpr uint32_t kNodeHalves = kNode / 2;            // 45
-constexpr uint32_t kRecordHalves = kNodeWords * 2;     // 48
-constexpr uint32_t kShareVecs = kShare / 16;           // 32
 constexpr uint32_t kProofsPerGroup = 4;
 
 __global__ __launch_bounds__(256) void k_prove(const uint8_t* __restrict__ eds, const uint16_t* __restrict__ index,
@@ -52,16 +49,7 @@ __global__ __launch_bounds__(256) void k_prove(const uint8_t* __restrict__ eds, 
     const prove::NodeAt a = prove::node_at(L, s, e1, lane);
     rec = (uint32_t)prove::index_record(W, q.axis, q.index, a.level, a.pos);
   }
-  uint16_t* out = reinterpret_cast<uint16_t*>(nodes + q.node0 * kNode);
-  const uint32_t halves = nn * kNodeHalves;
-  // every lane takes every turn (the trip count is the wave's), so the lane a record number
-  // is read from is always active
-  for (uint32_t base = 0; base < halves; base += 64) {
-    const uint32_t t = base + lane;
-    const uint32_t j = t < halves ? t / kNodeHalves : 0u;
-    const uint32_t r = (uint32_t)__shfl((int)rec, (int)j, 64);
-    if (t < halves) out[t] = index[(uint64_t)r * kRecordHalves + (t - j * kNodeHalves)];
-  }
+  copy_proof_nodes(rec, nn, index, reinterpret_cast<uint16_t*>(nodes + q.node0 * kNode), lane);
   if (!leaves) return;
   const uint4* cells = reinterpret_cast<const uint4*>(eds);
   uint4* lo = reinterpret_cast<uint4*>(leaves + q.leaf0 * kShare);

@@ -1,7 +1,8 @@
 // The batched NMT prover (nmt_prove.hip, api_prove.cpp): the tree index of a resident square,
 // the closed form of nmt ProveRange's node selection, and the per-proof table the kernel
-// reads. Everything above the launcher declarations is plain C++ with no HIP in it:
-// tools/prove_select_check.cpp includes this header alone and walks it on the host.
+// reads. Everything above the device part (the node copy k_prove and k_ns_emit share, the
+// launcher declarations) is plain C++ with no HIP in it: tools/prove_select_check.cpp includes
+// this header alone and walks it on the host.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -117,7 +118,29 @@ static_assert(sizeof(Request) == 32, "Request layout");
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 
+#include "cel_internal.hpp"
+
 namespace cel {
+
+constexpr uint32_t kNodeHalves = kNode / 2;         // 45
+constexpr uint32_t kRecordHalves = kNodeWords * 2;  // 48
+constexpr uint32_t kShareVecs = kShare / 16;        // 32
+
+// A proof's nn <= 64 nodes out of the index as packed 90-byte nodes at `out`, by one wave: lane
+// j < nn holds the record number of node j in `rec`. The wave copies the 45 * nn halfwords,
+// lane t the t-th of each 64: it takes the record number of node t / 45 from that node's lane
+// and reads halfword t % 45 of the record. Every lane takes every turn (the trip count is the
+// wave's), so the lane a record number is read from is always active.
+__device__ __forceinline__ void copy_proof_nodes(uint32_t rec, uint32_t nn, const uint16_t* __restrict__ index,
+                                                 uint16_t* out, uint32_t lane) {
+  const uint32_t halves = nn * kNodeHalves;
+  for (uint32_t base = 0; base < halves; base += 64) {
+    const uint32_t t = base + lane;
+    const uint32_t j = t < halves ? t / kNodeHalves : 0u;
+    const uint32_t r = (uint32_t)__shfl((int)rec, (int)j, 64);
+    if (t < halves) out[t] = index[(uint64_t)r * kRecordHalves + (t - j * kNodeHalves)];
+  }
+}
 
 // The index of the square at eds (nmt_kernels.hip: the single-square commit's leaf and level
 // kernels, every level written to its own place in d_index), the packed roots, and the DAH

@@ -89,6 +89,26 @@ def test_verify_entry_points_validate_without_a_device():
     assert small >= 96 * (1 + 8 + 1) and big >= 96 * (36000 * 10) and big < 2 * 96 * (36000 * 10)
 
 
+def test_verify_workspace_layouts():
+    """The two workspace sizes are part of the ABI (a caller allocates by them): the proof
+    table, a 32-byte namespace and a dword per leaf, 96-byte records of the leaves and of the
+    nodes with one root per proof, each part rounded up to 256 bytes. The namespace verifier
+    keeps one more leaf record per proof and one byte per leaf (at least one)."""
+    import celestia_eds._lib as L
+    lib = L.load()
+    a = lambda x: (x + 255) // 256 * 256
+
+    def inclusion(tl, tn, n):
+        return a(40 * n) + a(32 * n) + a(4 * tl) + a(96 * tl) + a(96 * (tn + n))
+
+    for n in (0, 1, 2, 100):
+        for tl in (0, 1, 63, 1000):
+            for tn in (0, 8, 800):
+                assert lib.cel_dev_nmt_verify_workspace_size(tl, tn, n) == inclusion(tl, tn, n), (n, tl, tn)
+                assert lib.cel_dev_nmt_verify_namespace_workspace_size(tl, tn, n) == \
+                    inclusion(tl + n, tn, n) + a(max(tl, 1)), (n, tl, tn)
+
+
 @pytest.mark.parametrize("n", [3, 13])
 def test_prove_range_matches_device_tree_order(n):
     """nmt_ref.Tree.prove_range lists nodes as nmt does: left siblings largest first (one per
