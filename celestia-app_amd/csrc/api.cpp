@@ -605,7 +605,7 @@ cel_status cel_codec_decode(cel_ctx* ctx, uint8_t* shards, const uint8_t* presen
   if ((e = hipMemcpyAsync(d_sh, shards, b, hipMemcpyHostToDevice, s)) != hipSuccess ||
       (e = hipMemcpyAsync(d_pr, present, 2 * n, hipMemcpyHostToDevice, s)) != hipSuccess)
     return hip_fail(ctx, e, "H2D");
-  if ((e = launch_rs_decode(d_sh, d_pr, 1, n, len, ctx->tables, nullptr, s)) != hipSuccess)
+  if ((e = launch_rs_decode(d_sh, d_pr, 1, n, len, ctx->tables, s)) != hipSuccess)
     return hip_fail(ctx, e, "decode");
   if ((e = hipMemcpyAsync(shards, d_sh, b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
@@ -622,7 +622,7 @@ cel_status cel_dev_decode(cel_ctx* ctx, void* d_shards, const void* d_present, u
   if (n > 1024) return fail(ctx, CEL_ETOOBIG, "too many shards for the device decoder");
   DeviceGuard g(ctx->device);
   const hipError_t e = launch_rs_decode(static_cast<uint8_t*>(d_shards), static_cast<const uint8_t*>(d_present), naxes,
-                                        n, len, ctx->tables, nullptr, pick_stream(ctx, stream));
+                                        n, len, ctx->tables, pick_stream(ctx, stream));
   return e == hipSuccess ? CEL_OK : hip_fail(ctx, e, "decode");
 }
 

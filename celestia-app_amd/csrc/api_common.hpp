@@ -1,5 +1,7 @@
-// Shared helpers of the C-ABI host layer (api.cpp, api_repair.cpp): error reporting with
-// the reference's messages, grow-only device scratch per ctx, device selection.
+// Shared helpers of the C-ABI host layer (every api_*.cpp): error reporting with the
+// reference's messages, grow-only device scratch and page-locked staging per ctx, the plan
+// buffer's upload rule, device selection, argument checks of a square, and the entry points
+// one api file lends another (blob commitments, the repair with the ctx lock held).
 #pragma once
 #include <hip/hip_runtime.h>
 

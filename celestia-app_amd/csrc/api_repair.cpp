@@ -1,12 +1,11 @@
 // C ABI of the repair (include/celestia_eds.h): cel_repair, cel_dev_repair and their test
-// hooks, split from api.cpp. Host-side control of rsmt2d's Repair over a device-resident
-// EDS; every decode, re-encode, compare and root runs in the HIP kernels.
+// hooks, split from api.cpp. Device control of rsmt2d's Repair over a device-resident
+// EDS: the buffers, the two streams and what is enqueued on them. What to solve and check,
+// and in which order, is the host planner's (repair_plan.hpp); every decode, re-encode,
+// compare and root runs in the HIP kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
-#include <cstdlib>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -14,9 +13,11 @@
 
 #include "api_common.hpp"
 #include "cel_internal.hpp"
+#include "repair_plan.hpp"
 
 using namespace cel;
 using namespace cel::abi;
+using namespace cel::repair;
 
 extern "C" {
 
@@ -44,16 +45,19 @@ struct RepairBufs {
   uint8_t* dchk;      // gathered axes of the check passes (side stream)
   uint8_t* dmask_chk;
   uint8_t* tmp;       // re-encoded parity halves (side stream)
-  uint8_t* work;      // NMT workspace of the final verification
+  uint8_t* work;      // NMT workspace of the final verification, or repair_exact's axes roots
+  uint32_t* rec;      // [2][W][kNodeWords] repair_exact's root records, in the same slot
   uint8_t* roots;     // [2][W][90] row then column roots of the final verification, then flags
-  uint8_t* hres;      // page-locked copy of roots + flags (one D2H at the end)
+  int32_t* flags;     // [2][W] encoding-check flags by (direction, axis), right after the roots
+  uint8_t* hroots;    // page-locked copy of roots + flags (one D2H of res_bytes at the end)
+  int32_t* hflags;
   size_t res_bytes;
   int32_t* idx;       // [kIdxSlots][W] device axis lists
   int32_t* hidx;      // [kIdxSlots][W] page-locked staging of the same
-  uint8_t* hmask;     // [W][W] page-locked staging of the presence mask
+  uint8_t* hmask;     // [W][W] page-locked staging of the presence mask, then of the first list
+  int32_t* hlist0;
   uint32_t slot;      // next free slot
   uint32_t solves;    // solve passes so far (which dense buffer is next)
-  int32_t* flags;     // [2][W] encoding-check flags by (direction, axis), right after the roots
   // Two streams: the solve chain (gather -> decode -> scatter) runs on `main`; every
   // re-encode check (of the solved axes, the sanity and the orthogonal checks) runs on
   // `side`, off the chain's critical path: its outcome is only read at the end.
@@ -62,6 +66,51 @@ struct RepairBufs {
   hipEvent_t ev_side[2];  // the side stream is done with dense[i]
   hipEvent_t ev_done;     // the side stream's last check
 };
+
+// The layout of each scratch slot and of the page-locked stage, one walk per buffer (b.W
+// set). carved() runs a walk: on a null base it gives the size to allocate, on the
+// allocation the pointers into it.
+static void carve_in(Carver& c, RepairBufs& b) {  // S_IN
+  for (uint8_t** p : {&b.dense[0], &b.dense[1], &b.dchk}) *p = c.take<uint8_t>((size_t)b.W * b.W * kShare);
+}
+static void carve_aux(Carver& c, RepairBufs& b) {  // S_AUX
+  b.tmp = c.take<uint8_t>((size_t)b.W * b.W * kShare / 2);
+  b.idx = c.take<int32_t>((size_t)kIdxSlots * b.W * 4);
+}
+// The presence mask, then the first pass's axis list directly after it: one upload carries
+// both, so the device buffer and the stage take them by the same walk.
+static void take_mask_list(Carver& c, uint32_t W, uint8_t** mask, int32_t** list0) {
+  *mask = c.take<uint8_t>((size_t)W * W);
+  *list0 = c.take<int32_t>((size_t)W * 4);
+}
+static void carve_mask(Carver& c, RepairBufs& b) {  // S_MASK
+  take_mask_list(c, b.W, &b.mask, &b.list0);
+  for (uint8_t** p : {&b.dmask, &b.dmask_chk}) *p = c.take<uint8_t>((size_t)b.W * b.W);
+}
+// Every root of the square, then the flags directly after them: one download (res_bytes,
+// from the first root to the last flag) brings both back, into the same walk of the stage.
+static void take_results(Carver& c, uint32_t W, uint8_t** roots, int32_t** flags) {
+  *roots = c.take<uint8_t>(2 * (size_t)W * kNode);
+  *flags = c.take<int32_t>(2 * (size_t)W * 4);
+}
+static void carve_roots(Carver& c, RepairBufs& b) { take_results(c, b.W, &b.roots, &b.flags); }  // S_ROOTS
+// repair_exact's axes-roots workspace of one direction's 2k axes, then, after it, the root
+// records of both directions; the whole-square commit's workspace lies over the two.
+static void carve_work(Carver& c, RepairBufs& b) {  // S_WORK
+  b.work = c.take<uint8_t>(axes_roots_workspace_size(b.W / 2, b.W));
+  b.rec = c.take<uint32_t>(2 * (size_t)b.W * kNodeWords * 4);
+  c.overlay(nmt_workspace_size(b.W / 2, 1));
+}
+static void carve_stage(Carver& c, RepairBufs& b) {  // the page-locked stage
+  b.hidx = c.take<int32_t>((size_t)kIdxSlots * b.W * 4);
+  take_mask_list(c, b.W, &b.hmask, &b.hlist0);  // hmask followed by its list
+  take_results(c, b.W, &b.hroots, &b.hflags);
+}
+static size_t carved(void (*walk)(Carver&, RepairBufs&), void* base, RepairBufs& b) {
+  Carver c(base);
+  walk(c, b);
+  return c.size();
+}
 
 // `list` into the next axis-list slot, uploaded on stream s. Every slot in flight: drain
 // both streams (the side stream's compares read the lists too), then reuse.
@@ -99,33 +148,27 @@ static cel_status fuzz(cel_ctx* ctx, hipStream_t s) {
 // b.tmp and k_cmp.
 static cel_status encode_check(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_col, uint32_t na, const uint8_t* dense,
                                const int32_t* idx, hipStream_t s) {
-  const uint32_t W = 2 * k;
+  const uint64_t axis_b = (uint64_t)2 * k * kShare, half_b = (uint64_t)k * kShare;
+  const bool fused = k == 256 || k == 512;  // GF(2^16): the register kernel compares with the parity half as it goes
+  int32_t* flags = b.flags + (size_t)is_col * 2 * k;
   RsGeom g{};
   g.in = dense;
-  g.in_sq = (uint64_t)na * W * kShare;
-  g.in_axis = (uint64_t)W * kShare;
-  g.in_shard = kShare;
-  g.out = b.tmp;
-  g.out_sq = (uint64_t)na * k * kShare;
-  g.out_axis = (uint64_t)k * kShare;
-  g.out_shard = kShare;
+  g.in_axis = axis_b;
+  g.out = fused ? const_cast<uint8_t*>(dense) + half_b : b.tmp;
+  g.out_axis = fused ? axis_b : half_b;
+  g.in_sq = na * g.in_axis;
+  g.out_sq = na * g.out_axis;
+  g.in_shard = g.out_shard = kShare;
   g.n = k;
   g.len = kShare;
   g.axes = na;
   g.nsq = 1;
+  g.chk_flags = fused ? flags : nullptr;
+  g.chk_idx = fused ? idx : nullptr;
   hipError_t e;
-  if (k == 256 || k == 512) {  // GF(2^16): the register kernel compares with the parity half as it goes
-    g.out = const_cast<uint8_t*>(dense) + (uint64_t)k * kShare;
-    g.out_sq = g.in_sq;
-    g.out_axis = g.in_axis;
-    g.chk_flags = b.flags + (size_t)is_col * W;
-    g.chk_idx = idx;
-    if ((e = launch_rs_encode(g, ctx->tables, s)) != hipSuccess) return hip_fail(ctx, e, "encoding check");
-    return CEL_OK;
-  }
-  if ((e = launch_rs_encode(g, ctx->tables, s)) != hipSuccess) return hip_fail(ctx, e, "re-encode");
-  if ((e = launch_cmp(b.tmp, (uint64_t)k * kShare, dense + (uint64_t)k * kShare, (uint64_t)W * kShare,
-                      (uint64_t)k * kShare, na, b.flags + (size_t)is_col * W, s, idx)) != hipSuccess)
+  if ((e = launch_rs_encode(g, ctx->tables, s)) != hipSuccess)
+    return hip_fail(ctx, e, fused ? "encoding check" : "re-encode");
+  if (!fused && (e = launch_cmp(b.tmp, half_b, dense + half_b, axis_b, half_b, na, flags, s, idx)) != hipSuccess)
     return hip_fail(ctx, e, "compare");
   return CEL_OK;
 }
@@ -143,17 +186,7 @@ static cel_status check_in_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int i
     return CEL_OK;
   }
   if (k == 256 || k == 512) {  // the GF(2^16) register kernel in check mode, in place
-    const uint64_t row = (uint64_t)W * kShare;
-    RsGeom g{};
-    g.in = b.eds;
-    g.out = b.eds + (is_col ? (uint64_t)k * row : (uint64_t)k * kShare);
-    g.in_axis = g.out_axis = is_col ? kShare : row;
-    g.in_shard = g.out_shard = is_col ? row : kShare;
-    g.in_sq = g.out_sq = row * W;
-    g.n = k;
-    g.len = kShare;
-    g.axes = na;
-    g.nsq = 1;
+    RsGeom g = square_axis_geom(b.eds, k, is_col, na, 1);
     g.chk_flags = b.flags + (size_t)is_col * W;
     g.chk_idx = idx;
     g.chk_axes = idx;
@@ -163,6 +196,22 @@ static cel_status check_in_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int i
   if ((e = launch_gather_axes(b.eds, b.mask, W, idx, is_col, na, b.dchk, b.dmask_chk, s)) != hipSuccess)
     return hip_fail(ctx, e, "gather");
   return encode_check(ctx, b, k, is_col, na, b.dchk, idx, s);
+}
+
+// Decode of na listed axes (rows, columns, or with is_col < 0 every entry's direction in
+// bit 30: the register decoder only) on stream s. W = 32 .. 256: the register decoder in
+// place, erased cells straight into the square (no gather / scatter on the chain); else
+// gather -> decode -> scatter through `dense`.
+static hipError_t decode_axes(cel_ctx* ctx, RepairBufs& b, uint32_t k, const int32_t* idx, int is_col, uint32_t na,
+                              uint8_t* dense, hipStream_t s) {
+  const uint32_t W = 2 * k;
+  if (rs_decode_axis_supported(W, kShare))
+    return launch_rs_decode_in_square(b.eds, b.mask, W, idx, is_col, na, ctx->tables.mul8, s);
+  hipError_t e;
+  if ((e = launch_gather_axes(b.eds, b.mask, W, idx, is_col, na, dense, b.dmask, s)) != hipSuccess ||
+      (e = launch_rs_decode(dense, b.dmask, na, k, kShare, ctx->tables, s)) != hipSuccess)
+    return e;
+  return launch_scatter_axes(b.eds, b.mask, W, idx, is_col, na, dense, s);
 }
 
 // rsmt2d solveCrossword's decode of `list` (incomplete axes of one direction), in two
@@ -188,21 +237,10 @@ static cel_status solve_issue(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_co
   if (uploaded) out->idx = uploaded;  // `list` is already on the device there
   else if ((st = upload_list(ctx, b, list, b.main, &out->idx)) != CEL_OK) return st;
   if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
-  const int32_t* idx = out->idx;
-  hipError_t e;
-  if (rs_decode_axis_supported(W, kShare)) {
-    // register decoder in place: erased cells straight into the square (no gather /
-    // scatter on the chain)
-    if ((e = launch_rs_decode_in_square(b.eds, b.mask, W, idx, is_col, na, ctx->tables.mul8, b.main)) != hipSuccess ||
-        (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
-      return hip_fail(ctx, e, "solve");
-    return CEL_OK;
-  }
-  uint8_t* dense = b.dense[d];
-  if ((e = hipStreamWaitEvent(b.main, b.ev_side[d], 0)) != hipSuccess ||  // the side stream is done with dense[d]
-      (e = launch_gather_axes(b.eds, b.mask, W, idx, is_col, na, dense, b.dmask, b.main)) != hipSuccess ||
-      (e = launch_rs_decode(dense, b.dmask, na, k, kShare, ctx->tables, nullptr, b.main)) != hipSuccess ||
-      (e = launch_scatter_axes(b.eds, b.mask, W, idx, is_col, na, dense, b.main)) != hipSuccess ||
+  hipError_t e = hipSuccess;
+  // dense path: the side stream is done with dense[d]
+  if (!rs_decode_axis_supported(W, kShare)) e = hipStreamWaitEvent(b.main, b.ev_side[d], 0);
+  if (e != hipSuccess || (e = decode_axes(ctx, b, k, out->idx, is_col, na, b.dense[d], b.main)) != hipSuccess ||
       (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
     return hip_fail(ctx, e, "solve");
   return CEL_OK;
@@ -245,166 +283,12 @@ static cel_status check_pass(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_col
   return check_in_square(ctx, b, k, is_col, na, idx, b.side);
 }
 
-// One check of the replay, in rsmt2d's order (oracle/eds.c orc_repair):
-//   SANITY  an axis complete before the repair: root (else "bad root input"), encoding
-//   SOLVE   an axis decoded by solve `solve`: encoding, root
-//   ORTH    an axis that solve `solve` completed: root, encoding
-struct Check {
-  enum Kind { SANITY, SOLVE, ORTH } kind;
-  int is_col;
-  int32_t idx;
-  int32_t solve;  // index into the solve log (-1 for SANITY)
-};
-struct Solve {
-  int is_col;
-  int32_t idx;
-};
-
 struct RepairOut {
   int32_t* bad_axis;
   int32_t* bad_index;
   uint8_t* byz_shares;   // nullable, W * 512
   uint8_t* byz_present;  // nullable, W
 };
-
-// a[i] bit j <-> a[j] bit i
-static void transpose64(uint64_t* a) {
-  uint64_t m = 0x00000000FFFFFFFFull;
-  for (int j = 32; j != 0; j >>= 1, m ^= (m << j)) {
-    for (int k = 0; k < 64; k = ((k | j) + 1) & ~j) {
-      const uint64_t t = ((a[k] >> j) ^ a[k | j]) & m;
-      a[k | j] ^= t;
-      a[k] ^= t << j;
-    }
-  }
-}
-
-// The presence mask as bitsets by row and by column (bit j of axis i = cell j of it) with
-// per-axis counts, so a solve's bookkeeping visits only the cells it fills.
-struct MaskBits {
-  uint32_t W, nw;
-  std::vector<uint64_t> bits[2];  // [is_col][axis * nw + word]
-  std::vector<uint32_t> cnt[2];
-  uint64_t total = 0;
-  MaskBits(const std::vector<uint8_t>& hm, uint32_t w) : W(w), nw((w + 63) / 64) {
-    const uint32_t P = nw * 64;  // padded to whole 64x64 tiles for the transpose
-    std::vector<uint64_t> rows((size_t)P * nw, 0), cols((size_t)P * nw, 0);
-    for (uint32_t i = 0; i < W; i++) {
-      const uint8_t* r = hm.data() + (size_t)i * W;
-      for (uint32_t j = 0; j < W; j += 8) {
-        uint64_t x = 0;
-        const uint32_t n = W - j < 8 ? W - j : 8;
-        std::memcpy(&x, r + j, n);  // bytes 0 / 1
-        rows[(size_t)i * nw + j / 64] |= ((x * 0x0102040810204080ull) >> 56) << (j % 64);
-      }
-    }
-    // cols = rows transposed, tile by tile
-    uint64_t t[64];
-    for (uint32_t bi = 0; bi < nw; bi++)
-      for (uint32_t bj = 0; bj < nw; bj++) {
-        for (int r = 0; r < 64; r++) t[r] = rows[(size_t)(bi * 64 + r) * nw + bj];
-        transpose64(t);
-        for (int r = 0; r < 64; r++) cols[(size_t)(bj * 64 + r) * nw + bi] = t[r];
-      }
-    rows.resize((size_t)W * nw);
-    cols.resize((size_t)W * nw);
-    bits[0] = std::move(rows);
-    bits[1] = std::move(cols);
-    for (int d = 0; d < 2; d++) {
-      cnt[d].assign(W, 0);
-      for (uint32_t i = 0; i < W; i++) {
-        uint32_t c = 0;
-        for (uint32_t q = 0; q < nw; q++) c += (uint32_t)__builtin_popcountll(bits[d][(size_t)i * nw + q]);
-        cnt[d][i] = c;
-      }
-    }
-    for (uint32_t i = 0; i < W; i++) total += cnt[0][i];
-  }
-  // A pass: every axis of `list` (direction is_col, ascending) gets all its cells.
-  // orth[t] = the orthogonal axes that solve list[t] completes, ascending: those whose
-  // missing cells all lie in listed axes, the last of them in list[t] (rsmt2d fills the
-  // axes one by one in list order). Word operations over the bitsets, O(W^2 / 64).
-  void fill_pass(int is_col, const std::vector<int32_t>& list, std::vector<std::vector<int32_t>>& orth) {
-    std::vector<uint64_t> S(nw, 0);
-    std::vector<int32_t> pos(W, -1);
-    for (size_t t = 0; t < list.size(); t++) {
-      S[(uint32_t)list[t] / 64] |= 1ull << ((uint32_t)list[t] % 64);
-      pos[list[t]] = (int32_t)t;
-    }
-    orth.assign(list.size(), {});
-    for (uint32_t j = 0; j < W; j++) {
-      if (cnt[!is_col][j] == W) continue;
-      uint64_t* a = bits[!is_col].data() + (size_t)j * nw;
-      bool inside = true;
-      int32_t last = -1;
-      uint32_t c = 0;
-      for (uint32_t q = 0; q < nw; q++) {
-        const uint64_t valid = (q + 1) * 64 <= W ? ~0ull : ((1ull << (W % 64)) - 1);
-        const uint64_t miss = ~a[q] & valid;
-        if (miss & ~S[q]) inside = false;
-        if (miss) last = (int32_t)(q * 64 + 63 - __builtin_clzll(miss));
-        a[q] |= S[q];
-        c += (uint32_t)__builtin_popcountll(a[q] & valid);
-      }
-      total += c - cnt[!is_col][j];
-      cnt[!is_col][j] = c;
-      if (inside && last >= 0) orth[pos[last]].push_back((int32_t)j);
-    }
-    for (int32_t i : list) {
-      uint64_t* a = bits[is_col].data() + (size_t)i * nw;
-      for (uint32_t q = 0; q < nw; q++) a[q] = (q + 1) * 64 <= W ? ~0ull : ((1ull << (W % 64)) - 1);
-      cnt[is_col][i] = W;
-    }
-  }
-};
-
-// The final verification's results, read back in one copy: every root of the square and
-// the encoding-check flags by (direction, axis).
-struct Verify {
-  const uint8_t* got;  // [2][W][90]
-  const int32_t* flags;
-  const uint8_t *row_roots, *col_roots;
-  uint32_t W;
-  bool root_ok(int is_col, int32_t i) const {
-    const uint8_t* exp = (is_col ? col_roots : row_roots) + (size_t)i * kNode;
-    return std::memcmp(got + (size_t)is_col * W * kNode + (size_t)i * kNode, exp, kNode) == 0;
-  }
-  bool enc_ok(int is_col, int32_t i) const { return flags[(size_t)is_col * W + i] == 0; }
-  // rsmt2d's order of checks: the first that fails (index into order, -1 if none) and
-  // its status
-  long first_failure(const std::vector<Check>& order, cel_status* code) const {
-    for (size_t t = 0; t < order.size(); t++) {
-      const Check& c = order[t];
-      bool ok = true;
-      *code = CEL_EBYZANTINE;
-      switch (c.kind) {
-        case Check::SANITY:
-          if (!root_ok(c.is_col, c.idx)) {
-            *code = CEL_EBADROOT;
-            ok = false;
-          } else {
-            ok = enc_ok(c.is_col, c.idx);
-          }
-          break;
-        case Check::SOLVE: ok = enc_ok(c.is_col, c.idx) && root_ok(c.is_col, c.idx); break;
-        case Check::ORTH: ok = root_ok(c.is_col, c.idx) && enc_ok(c.is_col, c.idx); break;
-      }
-      if (!ok) return (long)t;
-    }
-    return -1;
-  }
-};
-
-// hm := the presence mask before solve `upto` of `solves` (each solve completes its axis)
-static void rollback(std::vector<uint8_t>& hm, uint32_t W, const std::vector<Solve>& solves, size_t upto) {
-  for (size_t t = 0; t < upto; t++) {
-    const uint32_t i = (uint32_t)solves[t].idx;
-    if (solves[t].is_col)
-      for (uint32_t j = 0; j < W; j++) hm[(size_t)j * W + i] = 1;
-    else
-      std::memset(hm.data() + (size_t)i * W, 1, W);
-  }
-}
 
 // Report a failing axis: status, axis, index, and for CEL_EBYZANTINE rsmt2d's
 // ErrByzantineData.Shares: the axis's cells from the square (complete axes never change;
@@ -438,11 +322,10 @@ static cel_status fail_axis(cel_ctx* ctx, const RepairBufs& b, const std::vector
 }
 
 // Commit every root of the square on the main stream beside the side stream's last checks,
-// join the streams and read roots and flags back (one page-locked copy).
+// join the streams and read roots and flags back (one page-locked copy: b.hroots, b.hflags).
 static cel_status verify_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int last_col, const Issued& last,
-                                int pending_col, const std::vector<int32_t>& pending, Verify* v) {
-  const uint32_t W = 2 * k;
-  const size_t roots_b = (size_t)W * kNode;
+                                int pending_col, const std::vector<int32_t>& pending) {
+  const size_t roots_b = (size_t)b.W * kNode;
   hipError_t e;
   cel_status st;
   if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
@@ -456,12 +339,9 @@ static cel_status verify_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int las
     return hip_fail(ctx, e, "roots");
   if ((e = hipEventRecord(b.ev_done, b.side)) != hipSuccess || (e = hipStreamWaitEvent(b.main, b.ev_done, 0)) != hipSuccess)
     return hip_fail(ctx, e, "join");
-  if ((e = hipMemcpyAsync(b.hres, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
+  if ((e = hipMemcpyAsync(b.hroots, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
     return hip_fail(ctx, e, "D2H");
   if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  v->got = b.hres;
-  v->flags = reinterpret_cast<const int32_t*>(b.hres + (b.res_bytes - 2 * (size_t)W * 4));
-  v->W = W;
   return CEL_OK;
 }
 
@@ -469,82 +349,13 @@ static cel_status verify_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int las
 //
 // solveCrossword sweeps `for i { solveCrosswordRow(i); solveCrosswordCol(i) }`, and on
 // inconsistent data which axis fails first, and with which Shares, depends on that order.
-// The host replays the sweeps over the mask alone (every solve completes its axis): the
-// solve sequence, the orthogonal axes each solve completes, and each solve's level, one
-// more than the highest level among the solves that filled a cell it reads. Solves of one
-// level touch no cell another of them fills, so a level runs as one row and one column
-// launch; level by level the device sees every axis exactly as rsmt2d's sequence does.
-// hm0: the mask the repair started from; cells present in it still hold their bytes
-// (every decoder stores erased cells only).
-// rsmt2d's sweeps over the mask alone (every solve completes its axis): the solve
-// sequence, each solve's level and the check order (SOLVE, then the ORTH axes it
-// completes, ascending); cnt = known cells per axis at the end.
-struct SweepPlan {
-  std::vector<Solve> solves;
-  std::vector<int32_t> level;
-  std::vector<Check> order;
-  std::vector<uint32_t> cnt[2];
-  int32_t nlevels = 0;
-  bool solved = false;
-};
-
-static SweepPlan plan_sweeps(const std::vector<uint8_t>& hm, uint32_t k) {
-  const uint32_t W = 2 * k;
-  const size_t cells = (size_t)W * W;
-  SweepPlan p;
-  std::vector<uint8_t> m(hm);
-  p.cnt[0].assign(W, 0);
-  p.cnt[1].assign(W, 0);
-  auto& cnt = p.cnt;
-  size_t total = 0;
-  for (uint32_t i = 0; i < W; i++)
-    for (uint32_t j = 0; j < W; j++)
-      if (m[(size_t)i * W + j]) {
-        cnt[0][i]++;
-        cnt[1][j]++;
-        total++;
-      }
-  std::vector<int32_t> lvl_of(cells, 0);
-  p.solved = total == cells;
-  while (!p.solved) {
-    bool progress = false;
-    for (uint32_t i = 0; i < W; i++)
-      for (int d = 0; d < 2; d++) {
-        if (cnt[d][i] == W || cnt[d][i] < k) continue;
-        const size_t base_c = d ? i : (size_t)i * W, step = d ? W : 1;
-        int32_t L = 0;
-        for (uint32_t j = 0; j < W; j++) {
-          const size_t c = base_c + j * step;
-          if (m[c] && lvl_of[c] > L) L = lvl_of[c];
-        }
-        L++;
-        const int32_t si = (int32_t)p.solves.size();
-        p.order.push_back({Check::SOLVE, d, (int32_t)i, si});
-        for (uint32_t j = 0; j < W; j++) {
-          const size_t c = base_c + j * step;
-          if (m[c]) continue;
-          if (cnt[!d][j] == W - 1) p.order.push_back({Check::ORTH, !d, (int32_t)j, si});
-          m[c] = 1;
-          lvl_of[c] = L;
-          cnt[!d][j]++;
-          total++;
-        }
-        cnt[d][i] = W;
-        p.solves.push_back({d, (int32_t)i});
-        p.level.push_back(L);
-        if (L > p.nlevels) p.nlevels = L;
-        progress = true;
-      }
-    if (total == cells) p.solved = true;
-    if (!progress) break;
-  }
-  return p;
-}
-
-// Where repair_exact keeps its root records in b.work: after the axes-roots workspace of
-// one direction's 2k axes (repair_bufs sizes b.work to hold both).
-static size_t exact_rec_offset(uint32_t k) { return align256(axes_roots_workspace_size(k, 2 * k)); }
-
+// The host replays the sweeps over the mask alone (plan_sweeps): the solve sequence, the
+// orthogonal axes each solve completes, and each solve's level. Solves of one level touch
+// no cell another of them fills, so a level runs as one row and one column launch; level
+// by level the device sees every axis exactly as rsmt2d's sequence does. hm: the mask the
+// repair started from; cells present in it still hold their bytes (every decoder stores
+// erased cells only). Every check gathers its axes into dchk first, also where an in-place
+// check exists: the root kernel wants them dense anyway.
 static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>& hm, uint32_t k,
                                const uint8_t* row_roots, const uint8_t* col_roots, const RepairOut& out) {
   const Range range("repair.exact");
@@ -560,9 +371,8 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
   for (size_t o = 0; o < order.size(); o++)
     if (order[o].kind == Check::SOLVE) first[(size_t)order[o].solve] = o;
   const bool in_square = rs_decode_axis_supported(W, kShare);
-  // roots of the checked axes: 96-byte records after the axes-roots workspace (repair_bufs
-  // sizes b.work for both)
-  uint32_t* d_rec = reinterpret_cast<uint32_t*>(b.work + exact_rec_offset(k));
+  // roots of the checked axes: 96-byte records, each direction's in the order of its list
+  const uint8_t* const exp[2] = {row_roots, col_roots};
   std::vector<uint8_t> h_rec((size_t)2 * W * kNodeWords * 4);
   std::vector<int32_t> h_flags((size_t)2 * W);
   hipError_t e;
@@ -624,22 +434,15 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
     for (const Group& g : groups) {
       const int32_t* idx = b.idx + g.off;
       if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
-      if (in_square) {
-        e = launch_rs_decode_in_square(b.eds, b.mask, W, idx, g.is_col, g.n, ctx->tables.mul8, b.main);
-      } else if ((e = launch_gather_axes(b.eds, b.mask, W, idx, g.is_col, g.n, b.dense[0], b.dmask, b.main)) ==
-                     hipSuccess &&
-                 (e = launch_rs_decode(b.dense[0], b.dmask, g.n, k, kShare, ctx->tables, nullptr, b.main)) ==
-                     hipSuccess) {
-        e = launch_scatter_axes(b.eds, b.mask, W, idx, g.is_col, g.n, b.dense[0], b.main);
-      }
-      if (e != hipSuccess) return hip_fail(ctx, e, "solve");
+      if ((e = decode_axes(ctx, b, k, idx, g.is_col, g.n, b.dense[0], b.main)) != hipSuccess)
+        return hip_fail(ctx, e, "solve");
     }
     // encoding check and root of every checked axis, one direction at a time through dchk
     for (int d = 0; d < 2; d++) {
       const uint32_t na = (uint32_t)chk[d].size();
       if (!na) continue;
       const int32_t* idx = b.idx + (d ? off_chk1 : off_chk0);
-      uint32_t* rec = d_rec + (size_t)d * W * kNodeWords;
+      uint32_t* rec = b.rec + (size_t)d * W * kNodeWords;
       if ((e = launch_gather_axes(b.eds, b.mask, W, idx, d, na, b.dchk, b.dmask_chk, b.main)) != hipSuccess)
         return hip_fail(ctx, e, "gather");
       if ((st = encode_check(ctx, b, k, d, na, b.dchk, idx, b.main)) != CEL_OK) return st;
@@ -648,21 +451,17 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
     }
     if ((e = hipMemcpyAsync(h_flags.data(), b.flags, h_flags.size() * 4, hipMemcpyDeviceToHost, b.main)) !=
             hipSuccess ||
-        (e = hipMemcpyAsync(h_rec.data(), d_rec, h_rec.size(), hipMemcpyDeviceToHost, b.main)) != hipSuccess ||
+        (e = hipMemcpyAsync(h_rec.data(), b.rec, h_rec.size(), hipMemcpyDeviceToHost, b.main)) != hipSuccess ||
         (e = hipStreamSynchronize(b.main)) != hipSuccess)
       return hip_fail(ctx, e, "D2H");
     // replay the prefix's checks in sweep order
-    size_t pos[2] = {0, 0};
-    for (size_t o = first[s0]; o < first[s1]; o++) {
-      const Check& c = order[o];
-      const uint8_t* got = h_rec.data() + ((size_t)c.is_col * W + pos[c.is_col]++) * kNodeWords * 4;
-      const uint8_t* exp = (c.is_col ? col_roots : row_roots) + (size_t)c.idx * kNode;
-      const bool root_ok = std::memcmp(got, exp, kNode) == 0;
-      const bool enc_ok = h_flags[(size_t)c.is_col * W + (size_t)c.idx] == 0;
-      if (!root_ok || !enc_ok) {
-        rollback(hm, W, solves, (size_t)c.solve);
-        return fail_axis(ctx, b, hm, out, CEL_EBYZANTINE, c.is_col, c.idx, c.kind == Check::SOLVE);
-      }
+    cel_status code;
+    const long f = first_failure(order.data() + first[s0], first[s1] - first[s0],
+                                 {h_rec.data(), kNodeWords * 4, RootRecords::BY_RANK}, exp, h_flags.data(), W, &code);
+    if (f >= 0) {  // no SANITY check in a sweep plan: code is CEL_EBYZANTINE
+      const Check& c = order[first[s0] + (size_t)f];
+      rollback(hm, W, solves, (size_t)c.solve);
+      return fail_axis(ctx, b, hm, out, code, c.is_col, c.idx, c.kind == Check::SOLVE);
     }
   }
   // not reached for a square the pass schedule found byzantine (the outcome does not depend
@@ -704,24 +503,13 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
   // The first row pass goes to the device before the host builds its bookkeeping (the
   // mask bitsets, the sanity lists), which then runs beside the decode; its axis list
   // rides in the mask's upload.
-  std::vector<int32_t> list, orth, first;
-  for (uint32_t i = 0; i < W; i++) {  // hm bytes are 0 / 1: a word's popcount is its count
-    const uint8_t* r = hm.data() + (size_t)i * W;
-    uint32_t c = 0;
-    uint32_t j = 0;
-    for (; j + 8 <= W; j += 8) {
-      uint64_t x;
-      std::memcpy(&x, r + j, 8);
-      c += (uint32_t)__builtin_popcountll(x);
-    }
-    for (; j < W; j++) c += r[j];
-    if (c >= k && c < W) first.push_back((int32_t)i);
-  }
-  const size_t cells_a = align256(cells);
+  std::vector<int32_t> list, orth;
+  const std::vector<int32_t> first = first_row_pass(hm, k);
   std::memcpy(b.hmask, hm.data(), cells);
-  if (!first.empty()) std::memcpy(b.hmask + cells_a, first.data(), first.size() * 4);
+  if (!first.empty()) std::memcpy(b.hlist0, first.data(), first.size() * 4);
+  const size_t up_b = (size_t)(reinterpret_cast<uint8_t*>(b.hlist0) - b.hmask) + first.size() * 4;
   // the flags are the side stream's (its checks), zeroed there after the mask is up
-  if ((e = hipMemcpyAsync(b.mask, b.hmask, cells_a + first.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
+  if ((e = hipMemcpyAsync(b.mask, b.hmask, up_b, hipMemcpyHostToDevice, s)) != hipSuccess ||
       (e = hipEventRecord(b.ev_main, s)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess ||
       (e = hipMemsetAsync(b.flags, 0, 2 * (size_t)W * 4, b.side)) != hipSuccess)
     return hip_fail(ctx, e, "H2D");
@@ -762,11 +550,8 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
     bool progress = false;
     for (int is_col = 0; is_col < 2; is_col++) {
       list.clear();
-      orth.clear();
-      for (uint32_t i = 0; i < W; i++) {
-        const uint32_t c = mb.cnt[is_col][i];
-        if (c >= k && c < W) list.push_back((int32_t)i);
-      }
+      for (uint32_t i = 0; i < W; i++)
+        if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) list.push_back((int32_t)i);
       if (list.empty()) continue;
       if (first_issued) {  // the first row pass (the same list, issued above)
         first_issued = false;
@@ -784,16 +569,7 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
       // orthogonal axes whose last missing cell it held
       const Range fill_range("repair.fill");
       mb.fill_pass(is_col, list, by_solve);
-      for (size_t t = 0; t < list.size(); t++) {
-        const int32_t si = (int32_t)solves.size();
-        order.push_back({Check::SOLVE, is_col, list[t], si});
-        for (int32_t j : by_solve[t]) {
-          order.push_back({Check::ORTH, !is_col, j, si});
-          orth.push_back(j);
-        }
-        solves.push_back({is_col, list[t]});
-      }
-      std::sort(orth.begin(), orth.end());
+      log_pass(is_col, list, by_solve, order, solves, orth);
       // pending is empty here: the previous pass's orthogonal checks were issued (and
       // cleared) right after this pass's solve above, or this is the first pass
       pending.swap(orth);
@@ -806,10 +582,10 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
     }
     if (!progress) break;
   }
-  Verify v{nullptr, nullptr, row_roots, col_roots, W};
-  if ((st = verify_square(ctx, b, k, prev_col, prev, pending_col, pending, &v)) != CEL_OK) return st;
+  if ((st = verify_square(ctx, b, k, prev_col, prev, pending_col, pending)) != CEL_OK) return st;
+  const uint8_t* const exp[2] = {row_roots, col_roots};
   cel_status code;
-  const long f = v.first_failure(order, &code);
+  const long f = first_failure(order.data(), order.size(), {b.hroots, kNode, RootRecords::BY_AXIS}, exp, b.hflags, W, &code);
   if (f >= 0) {
     const Check& c = order[(size_t)f];
     if (c.kind == Check::SANITY) return fail_axis(ctx, b, hm, out, code, c.is_col, c.idx, false);
@@ -824,39 +600,21 @@ static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>&
 }
 
 static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs* b) {
-  const uint32_t W = 2 * k;
-  const size_t cells = (size_t)W * W, eds_b = cells * kShare;
-  const size_t cells_a = align256(cells);
   hipError_t e = hipSuccess;
-  b->W = W;
-  if (own_eds) b->eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, eds_b, &e));
-  b->dense[0] = static_cast<uint8_t*>(scratch(ctx, S_IN, 3 * eds_b, &e));
-  b->tmp = static_cast<uint8_t*>(scratch(ctx, S_AUX, eds_b / 2 + (size_t)kIdxSlots * W * 4 + 256, &e));
-  const size_t list_a = align256((size_t)W * 4);
-  b->mask = static_cast<uint8_t*>(scratch(ctx, S_MASK, 3 * cells_a + list_a, &e));
-  // the whole-square commit's workspace, or repair_exact's: the axes-roots workspace of one
-  // direction's axes, then the root records of both directions
-  const size_t work_b = std::max(nmt_workspace_size(k, 1), exact_rec_offset(k) + 2 * (size_t)W * kNodeWords * 4);
-  b->work = static_cast<uint8_t*>(scratch(ctx, S_WORK, work_b, &e));
-  const size_t roots_a = align256(2 * (size_t)W * kNode);
-  b->res_bytes = roots_a + 2 * (size_t)W * 4;
-  b->roots = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, b->res_bytes, &e));
-  if (!b->eds || !b->dense[0] || !b->tmp || !b->mask || !b->work || !b->roots)
+  b->W = 2 * k;
+  if (own_eds) b->eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, (size_t)b->W * b->W * kShare, &e));
+  if (!b->eds) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+  auto slot = [&](int sl, void (*walk)(Carver&, RepairBufs&)) {
+    void* p = scratch(ctx, sl, carved(walk, nullptr, *b), &e);
+    if (p) carved(walk, p, *b);
+    return p != nullptr;
+  };
+  if (!slot(S_IN, carve_in) || !slot(S_AUX, carve_aux) || !slot(S_MASK, carve_mask) || !slot(S_WORK, carve_work) ||
+      !slot(S_ROOTS, carve_roots))
     return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  b->dense[1] = b->dense[0] + eds_b;
-  b->dchk = b->dense[1] + eds_b;
-  b->list0 = reinterpret_cast<int32_t*>(b->mask + cells_a);
-  b->dmask = b->mask + cells_a + list_a;
-  b->dmask_chk = b->dmask + cells_a;
-  b->flags = reinterpret_cast<int32_t*>(b->roots + roots_a);
-  b->idx = reinterpret_cast<int32_t*>(b->tmp + eds_b / 2);
-  const size_t cells_h = align256(cells);
-  // axis lists, mask + first list, results
-  const size_t hb = (size_t)kIdxSlots * W * 4 + cells_h + list_a + b->res_bytes;
-  if (!host_stage(ctx, hb)) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  b->hidx = static_cast<int32_t*>(ctx->hstage);
-  b->hmask = static_cast<uint8_t*>(ctx->hstage) + (size_t)kIdxSlots * W * 4;
-  b->hres = b->hmask + cells_h + list_a;
+  b->res_bytes = (size_t)(reinterpret_cast<uint8_t*>(b->flags) - b->roots) + 2 * (size_t)b->W * 4;  // roots .. last flag
+  if (!host_stage(ctx, carved(carve_stage, nullptr, *b))) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
+  carved(carve_stage, ctx->hstage, *b);
   b->slot = 0;
   b->solves = 0;
   // the side stream and the events are the batch pipeline's (the ctx lock is held)
@@ -872,36 +630,46 @@ static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs
   return CEL_OK;
 }
 
-}  // namespace
+// Both entry points with ctx->mu held: the repair of the caller's device square d_eds, or,
+// with d_eds null, of the host square h_eds through the ctx's own buffer (uploaded before,
+// downloaded after). `present` is handed back whenever the repair itself ran to an outcome.
+static cel_status repair_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds, uint8_t* present, uint32_t k,
+                                uint32_t share_size, const uint8_t* row_roots, const uint8_t* col_roots,
+                                const RepairOut& out) {
+  if ((!h_eds && !d_eds) || !present || !row_roots || !col_roots) return fail(ctx, CEL_EINVAL, "nil argument");
+  cel_status st = validate_square(ctx, k, share_size);
+  if (st) return st;
+  if (out.bad_axis) *out.bad_axis = -1;
+  if (out.bad_index) *out.bad_index = -1;
+  DeviceGuard g(ctx->device);
+  const size_t cells = (size_t)4 * k * k, eds_b = cells * kShare;
+  RepairBufs b{};
+  b.eds = static_cast<uint8_t*>(d_eds);
+  if ((st = repair_bufs(ctx, k, !d_eds, &b)) != CEL_OK) return st;
+  hipStream_t s = ctx->stream;
+  hipError_t e;
+  std::vector<uint8_t> hm = normalise_mask(present, cells);
+  if (!d_eds && (e = hipMemcpyAsync(b.eds, h_eds, eds_b, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(ctx, e, "H2D");
+  st = repair_core(ctx, b, hm, k, row_roots, col_roots, out);
+  if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
+  if (!d_eds) {  // the (partially) repaired square goes back either way, with the mask it is valid under
+    if ((e = hipMemcpyAsync(h_eds, b.eds, eds_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
+  }
+  std::memcpy(present, hm.data(), cells);
+  return st;
+}
 
+}  // namespace
 
 cel_status cel_repair(cel_ctx* ctx, uint8_t* eds, uint8_t* present, uint32_t k, uint32_t share_size,
                       const uint8_t* row_roots, const uint8_t* col_roots, int32_t* bad_axis, int32_t* bad_index,
                       uint8_t* byz_shares, uint8_t* byz_present) {
   if (!ctx) return CEL_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  if (!eds || !present || !row_roots || !col_roots) return fail(ctx, CEL_EINVAL, "nil argument");
-  cel_status st = validate_square(ctx, k, share_size);
-  if (st) return st;
-  if (bad_axis) *bad_axis = -1;
-  if (bad_index) *bad_index = -1;
-  DeviceGuard g(ctx->device);
-  const uint32_t W = 2 * k;
-  const size_t cells = (size_t)W * W, eds_b = cells * kShare;
-  RepairBufs b{};
-  if ((st = repair_bufs(ctx, k, true, &b)) != CEL_OK) return st;
-  hipStream_t s = ctx->stream;
-  hipError_t e;
-  std::vector<uint8_t> hm(cells);
-  for (size_t i = 0; i < cells; i++) hm[i] = present[i] != 0;
-  if ((e = hipMemcpyAsync(b.eds, eds, eds_b, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
-  st = repair_core(ctx, b, hm, k, row_roots, col_roots, RepairOut{bad_axis, bad_index, byz_shares, byz_present});
-  if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
-  // the (partially) repaired square goes back either way, with the mask it is valid under
-  if ((e = hipMemcpyAsync(eds, b.eds, eds_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  std::memcpy(present, hm.data(), cells);
-  return st;
+  return repair_locked(ctx, eds, nullptr, present, k, share_size, row_roots, col_roots,
+                       RepairOut{bad_axis, bad_index, byz_shares, byz_present});
 }
 
 cel_status cel_debug_repair_plan(const uint8_t* present, uint32_t k, int32_t* solve_axis, int32_t* solve_index,
@@ -909,10 +677,7 @@ cel_status cel_debug_repair_plan(const uint8_t* present, uint32_t k, int32_t* so
   if (!present || !solve_axis || !solve_index || !solve_level || !nsolves || !solved || !k || (k & (k - 1)) ||
       k > 512)
     return CEL_EINVAL;
-  const size_t cells = (size_t)4 * k * k;
-  std::vector<uint8_t> hm(cells);
-  for (size_t i = 0; i < cells; i++) hm[i] = present[i] != 0;
-  const SweepPlan p = plan_sweeps(hm, k);
+  const SweepPlan p = plan_sweeps(normalise_mask(present, (size_t)4 * k * k), k);
   for (size_t t = 0; t < p.solves.size(); t++) {
     solve_axis[t] = p.solves[t].is_col;
     solve_index[t] = p.solves[t].idx;
@@ -946,20 +711,6 @@ cel_status cel_dev_repair(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t 
 cel_status cel::abi::dev_repair_locked(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t k,
                                        const uint8_t* row_roots, const uint8_t* col_roots, int32_t* bad_axis,
                                        int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present) {
-  if (!d_eds || !present || !row_roots || !col_roots) return fail(ctx, CEL_EINVAL, "nil argument");
-  cel_status st = validate_square(ctx, k, kShare);
-  if (st) return st;
-  if (bad_axis) *bad_axis = -1;
-  if (bad_index) *bad_index = -1;
-  DeviceGuard g(ctx->device);
-  const size_t cells = (size_t)4 * k * k;
-  RepairBufs b{};
-  b.eds = static_cast<uint8_t*>(d_eds);
-  if ((st = repair_bufs(ctx, k, false, &b)) != CEL_OK) return st;
-  std::vector<uint8_t> hm(cells);
-  for (size_t i = 0; i < cells; i++) hm[i] = present[i] != 0;
-  st = repair_core(ctx, b, hm, k, row_roots, col_roots, RepairOut{bad_axis, bad_index, byz_shares, byz_present});
-  if (st == CEL_OK || st == CEL_EBYZANTINE || st == CEL_EBADROOT || st == CEL_EUNREPAIRABLE)
-    std::memcpy(present, hm.data(), cells);
-  return st;
+  return repair_locked(ctx, nullptr, d_eds, present, k, kShare, row_roots, col_roots,
+                       RepairOut{bad_axis, bad_index, byz_shares, byz_present});
 }

@@ -78,6 +78,11 @@ struct Carver {
     off += align256(bytes);
     return p;
   }
+  // Another use of the same memory, `bytes` long from the base, lies over the regions taken
+  // so far: the workspace holds whichever is longer.
+  void overlay(size_t bytes) {
+    if (off < align256(bytes)) off = align256(bytes);
+  }
   size_t size() const { return off; }
 };
 
@@ -109,10 +114,16 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb) {
 hipError_t upload_tables(DeviceTables* t);
 void free_tables(DeviceTables* t);
 
-// Kernel launchers (the rs_*.hip files; nmt_kernels.hip the EDS commit, nmt_slab.hip the
-// row-sharded mode, nmt_trees.hip single trees, axes roots, exported trees and byte slices).
-// All asynchronous on `s`.
+// Kernel launchers, all asynchronous on `s`. Declared here: the rs_*.hip files (encode,
+// decode, encoding check), nmt_kernels.hip (the EDS commit), nmt_slab.hip (the row-sharded
+// mode), nmt_trees.hip (single trees, axes roots, exported trees, byte slices),
+// repair_kernels.hip, blob_commit.hip, square_build.hip and probe_kernels.hip. The proof
+// kernels declare theirs beside their layouts: nmt_verify.hpp, nmt_prove.hpp,
+// nmt_namespace.hpp.
 hipError_t launch_rs_encode(const RsGeom& g, const DeviceTables& t, hipStream_t s);
+// The geometry of `axes` whole axes of nsq resident squares encoded in place: rows
+// (is_col == 0) or columns from axis 0 on, data half in, parity half out.
+RsGeom square_axis_geom(uint8_t* eds, uint32_t k, int is_col, uint32_t axes, uint32_t nsq);
 hipError_t launch_rs_encode_bitslice(const RsGeom& g, hipStream_t s);  // GF(2^8), n <= 16
 hipError_t launch_rs_encode_axis(const RsGeom& g, hipStream_t s);       // GF(2^8), 32 <= n <= 128
 // Two launches' worth of GF(2^8) axes (same n, len, axes count and squares, no data copy) in
@@ -261,8 +272,7 @@ hipError_t launch_rs_encode_gf16p(const RsGeom& g, const DeviceTables& t, hipStr
 hipError_t launch_rs_decode_gf16(uint8_t* shards, const uint8_t* present, uint32_t naxes, uint32_t n, uint32_t len,
                                  const DeviceTables& t, hipStream_t s);
 hipError_t launch_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t naxes, uint32_t n,
-                            uint32_t len, const DeviceTables& t, void* work, hipStream_t s);
-size_t decode_workspace_size(uint32_t naxes, uint32_t n);
+                            uint32_t len, const DeviceTables& t, hipStream_t s);
 // GF(2^8) register-resident decode (rs_decode_axis.hip): n = 32..256 points, len % 64 == 0.
 bool rs_decode_axis_supported(uint32_t n, uint32_t len);
 hipError_t launch_rs_decode_axis(uint8_t* shards, const uint8_t* present, uint32_t naxes, uint32_t n, uint32_t len,

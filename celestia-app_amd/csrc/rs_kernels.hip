@@ -205,52 +205,39 @@ hipError_t launch_rs_encode(const RsGeom& g, const DeviceTables& t, hipStream_t 
   return launch_rs_encode_gf16p(g, t, s);  // n = 1024, 2048 (no data copy, linear placement)
 }
 
+RsGeom square_axis_geom(uint8_t* eds, uint32_t k, int is_col, uint32_t axes, uint32_t nsq) {
+  const uint64_t row = (uint64_t)2 * k * kShare;  // bytes per EDS row
+  RsGeom g{};
+  g.in = eds;
+  g.out = eds + (is_col ? (uint64_t)k * row : (uint64_t)k * kShare);
+  g.in_sq = g.out_sq = (uint64_t)4 * k * k * kShare;
+  g.in_axis = g.out_axis = is_col ? kShare : row;
+  g.in_shard = g.out_shard = is_col ? row : kShare;
+  g.n = k;
+  g.len = kShare;
+  g.axes = axes;
+  g.nsq = nsq;
+  return g;
+}
+
 // Row pass of the extension, Q0 rows -> Q1. Q0 is read from `ods` (and copied into the
 // EDS by the row pass) when ods != nullptr, else from the EDS itself.
 static RsGeom row_geom(const uint8_t* ods, uint8_t* eds, uint32_t k, uint32_t nsq) {
-  const uint64_t row = (uint64_t)2 * k * kShare;  // bytes per EDS row
-  const uint64_t sq_eds = (uint64_t)4 * k * k * kShare;
-  const uint64_t sq_ods = (uint64_t)k * k * kShare;
-  RsGeom r{};
-  r.in = ods ? ods : eds;
-  r.in_sq = ods ? sq_ods : sq_eds;
-  r.in_axis = ods ? (uint64_t)k * kShare : row;
-  r.in_shard = kShare;
-  if (ods) {
+  RsGeom r = square_axis_geom(eds, k, 0, k, nsq);
+  if (ods) {  // the copy into Q0 takes the in-place input's place
     r.dcopy = eds;
-    r.dc_sq = sq_eds;
-    r.dc_axis = row;
+    r.dc_sq = r.in_sq;
+    r.dc_axis = r.in_axis;
     r.dc_shard = kShare;
+    r.in = ods;
+    r.in_sq = (uint64_t)k * k * kShare;
+    r.in_axis = (uint64_t)k * kShare;
   }
-  r.out = eds + (uint64_t)k * kShare;
-  r.out_sq = sq_eds;
-  r.out_axis = row;
-  r.out_shard = kShare;
-  r.n = k;
-  r.len = kShare;
-  r.axes = k;
-  r.nsq = nsq;
   return r;
 }
 
 // columns of [Q0|Q1] -> [Q2|Q3] (all 2k columns, after every row)
-static RsGeom col_geom(uint8_t* eds, uint32_t k, uint32_t nsq) {
-  const uint64_t row = (uint64_t)2 * k * kShare;  // bytes per EDS row
-  RsGeom cols{};
-  cols.in = eds;
-  cols.in_sq = (uint64_t)4 * k * k * kShare;
-  cols.in_axis = kShare;
-  cols.in_shard = row;
-  cols.out = eds + (uint64_t)k * row;
-  cols.out_sq = cols.in_sq;
-  cols.out_axis = kShare;
-  cols.out_shard = row;
-  cols.n = k;
-  cols.len = kShare;
-  cols.axes = 2 * k;
-  cols.nsq = nsq;
-  return cols;
-}
+static RsGeom col_geom(uint8_t* eds, uint32_t k, uint32_t nsq) { return square_axis_geom(eds, k, 1, 2 * k, nsq); }
 
 hipError_t launch_extend(const uint8_t* ods, uint8_t* eds, uint32_t k, uint32_t nsq, const DeviceTables& t,
                          hipStream_t s) {
@@ -532,10 +519,8 @@ __global__ __launch_bounds__(256) void k_rs_decode(uint8_t* shards, const uint8_
   }
 }
 
-size_t decode_workspace_size(uint32_t, uint32_t) { return 0; }
-
 hipError_t launch_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t naxes, uint32_t m, uint32_t len,
-                            const DeviceTables& t, void*, hipStream_t s) {
+                            const DeviceTables& t, hipStream_t s) {
   if (!naxes) return hipSuccess;
   const uint32_t n = 2 * m;
   if (rs_decode_axis_supported(n, len)) return launch_rs_decode_axis(shards, present, naxes, n, len, t.mul8, s);
