@@ -16,22 +16,26 @@
 // CEL_EDEVICE.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <climits>
-#include <cstdlib>
-#include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <memory>
 #include <string>
-#include <vector>
 
 #include "api_common.hpp"
 #include "cel_internal.hpp"
+#include "extend_plan.hpp"
 
 using namespace cel;
 using namespace cel::abi;
 
+// f(event) for every event a ctx creates with itself (the staged uploads' events and
+// ev_sq_done are made on first use).
+template <class F>
+static void each_event(cel_ctx* c, F f) {
+  for (hipEvent_t* ev : {&c->ev_start, &c->ev_ext, &c->ev_cols, &c->ev_dl, &c->ev_repair_main, &c->ev_repair_side[0],
+                         &c->ev_repair_side[1], &c->ev_repair_done})
+    f(*ev);
+  for (uint32_t i = 0; i < ext::kHostChunks; i++) f(c->ev_extended[i]), f(c->ev_committed[i]);
+  for (uint32_t i = 0; i < ext::kUp; i++) f(c->ev_up[i]), f(c->ev_rows[i]);
+}
 
 extern "C" {
 
@@ -46,16 +50,12 @@ cel_status cel_ctx_create(int device, cel_ctx** out) {
   DeviceGuard g(device);
   hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
   for (int i = 0; i < cel_ctx::kPipe && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&ctx->sub[i], hipStreamNonBlocking);
-  for (int i = 0; i < cel_ctx::kChunks && e == hipSuccess; i++) {
-    e = hipEventCreateWithFlags(&ctx->ev_done[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_rs[i], hipEventDisableTiming);
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_start, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_ext, hipEventDisableTiming);
-  for (int i = 0; i < cel_ctx::kPipe && e == hipSuccess; i++) {
-    e = hipEventCreateWithFlags(&ctx->ev_dl[i], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->dl[i], hipStreamNonBlocking);
-  }
+  // the events between the two groups of streams, where they have always been created (made
+  // after the dl streams, cel_extend_batch measured slower: profiles/extend_host_refactor_ab.txt)
+  each_event(ctx, [&](hipEvent_t& ev) {
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  });
+  for (int i = 0; i < cel_ctx::kPipe && e == hipSuccess; i++) e = hipStreamCreateWithFlags(&ctx->dl[i], hipStreamNonBlocking);
   if (e == hipSuccess) e = upload_tables(&ctx->tables);
   if (e != hipSuccess) {
     cel_ctx_destroy(ctx);
@@ -76,32 +76,28 @@ void cel_ctx_destroy(cel_ctx* ctx) {
       (void)hipEventSynchronize(ctx->ev_sq_done);  // a caller stream may still read the square plan
       (void)hipEventDestroy(ctx->ev_sq_done);
     }
-    if (ctx->ev_sq_up) (void)hipEventDestroy(ctx->ev_sq_up);
-    if (ctx->sq_stage) (void)hipHostFree(ctx->sq_stage);
+    // the square plan's upload precedes ev_sq_done on its stream: waited for already
+    if (ctx->square_up.ev) (void)hipEventDestroy(ctx->square_up.ev);
+    if (ctx->square_up.buf) (void)hipHostFree(ctx->square_up.buf);
     for (int i = 0; i < cel_ctx::kScratch; i++)
       if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->hstage) (void)hipHostFree(ctx->hstage);
-    if (ctx->ev_plan) {
-      (void)hipEventSynchronize(ctx->ev_plan);  // a caller stream may still read plan_stage
-      (void)hipEventDestroy(ctx->ev_plan);
+    if (ctx->plan_up.ev) {
+      (void)hipEventSynchronize(ctx->plan_up.ev);  // a caller stream may still read the plan buffer
+      (void)hipEventDestroy(ctx->plan_up.ev);
     }
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
+    if (ctx->plan_up.buf) (void)hipHostFree(ctx->plan_up.buf);
     free_tables(&ctx->tables);
     for (int i = 0; i < cel_ctx::kPipe; i++)
       if (ctx->sub[i]) (void)hipStreamDestroy(ctx->sub[i]);
-    for (int i = 0; i < cel_ctx::kChunks; i++) {
-      if (ctx->ev_done[i]) (void)hipEventDestroy(ctx->ev_done[i]);
-      if (ctx->ev_rs[i]) (void)hipEventDestroy(ctx->ev_rs[i]);
-    }
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_ext) (void)hipEventDestroy(ctx->ev_ext);
-    for (int i = 0; i < cel_ctx::kPipe; i++) {
+    for (int i = 0; i < cel_ctx::kPipe; i++)
       if (ctx->dl[i]) {
         (void)hipStreamSynchronize(ctx->dl[i]);
         (void)hipStreamDestroy(ctx->dl[i]);
       }
-      if (ctx->ev_dl[i]) (void)hipEventDestroy(ctx->ev_dl[i]);
-    }
+    each_event(ctx, [](hipEvent_t& ev) {
+      if (ev) (void)hipEventDestroy(ev);
+    });
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   }
   delete ctx;
@@ -146,44 +142,10 @@ cel_status cel_device_name(cel_ctx* ctx, char* buf, size_t len) {
 
 // ------------------------------------------------------------------ squares
 
-// Chunking of a batch over the internal streams: chunk c runs RS extension then NMT +
-// DAH on stream sub[c % kPipe]; the chunks start together, so one chunk's latency-bound
-// tree top + DAH runs beside the other's work. Two chunks (profiles/r1g_pipe_chunks_ab.txt);
-// chaining the extensions so each runs beside the previous chunk's hashing buys nothing,
-// the step is the sum of the two VALU-bound phases (profiles/r2_pipe_overlap_ab.txt).
-// Equal halves: uneven splits (5/8 .. 7/8 of the batch in the first chunk, so the small
-// chunk's tree top would run under the large chunk's bulk) measured slower at both k=64
-// B=128 and k=128 B=256 (profiles/r4_pipe_split_ab.txt).
-constexpr uint32_t kPipeChunks = 2;
-
-struct PipePlan {
-  uint32_t nchunks;
-  uint32_t first[kPipeChunks], cnt[kPipeChunks];
-  size_t work_off[kPipeChunks], work_bytes;  // NMT workspace of each chunk
-};
-
-static PipePlan pipe_plan(uint32_t k, uint32_t n) {
-  PipePlan p{};
-  uint32_t c0 = n < 2 ? n : (n + 1) / 2;
-  if (c0 >= n) c0 = n;
-  if (c0 == 0) c0 = n;
-  p.nchunks = c0 < n ? 2 : 1;
-  p.first[0] = 0;
-  p.cnt[0] = c0;
-  p.first[1] = c0;
-  p.cnt[1] = n - c0;
-  size_t off = 0;
-  for (uint32_t c = 0; c < p.nchunks; c++) {
-    p.work_off[c] = off;
-    off += align256(nmt_workspace_size(k, p.cnt[c]));
-  }
-  p.work_bytes = off;
-  return p;
+// The device batch's chunks (extend_plan.hpp), each with its 256-aligned NMT workspace.
+static ext::PipePlan pipe_plan(uint32_t k, uint32_t n) {
+  return ext::pipe_plan(k, n, [](uint32_t kk, uint32_t cnt) { return align256(nmt_workspace_size(kk, cnt)); });
 }
-
-// Chunks of the host-buffer pipeline: the upload of chunk c + 1, the compute of chunk c
-// and the copy-back of chunk c - 1 overlap (profiles/r1c_host_io.txt).
-constexpr uint32_t kHostChunks = 4;
 
 void* cel_host_alloc(size_t bytes) {
   void* p = nullptr;
@@ -254,7 +216,7 @@ cel_status cel_dev_extend_batch(cel_ctx* ctx, const void* d_ods, uint32_t n, uin
   cel_status st = validate_square(ctx, k, kShare);
   if (st) return st;
   DeviceGuard g(ctx->device);
-  const PipePlan plan = pipe_plan(k, n);
+  const ext::PipePlan plan = pipe_plan(k, n);
   const uint64_t ods_sq = (uint64_t)k * k * kShare, eds_sq = 4 * ods_sq, roots_sq = (uint64_t)2 * k * kNode;
   hipStream_t us = pick_stream(ctx, stream);
   if (flags & CEL_FLAG_CALLER_STREAM) {
@@ -279,7 +241,7 @@ cel_status cel_dev_extend_batch(cel_ctx* ctx, const void* d_ods, uint32_t n, uin
   hipError_t e = hipEventRecord(ctx->ev_start, us);
   for (uint32_t c = 0; c < plan.nchunks && e == hipSuccess; c++) {
     const uint32_t first = plan.first[c], cnt = plan.cnt[c];
-    hipStream_t s = ctx->sub[c % cel_ctx::kPipe];
+    hipStream_t s = ctx->sub[c];
     if ((e = hipStreamWaitEvent(s, ctx->ev_start, 0)) != hipSuccess) break;
     const uint8_t* ods = d_ods ? static_cast<const uint8_t*>(d_ods) + first * ods_sq : nullptr;
     uint8_t* eds = static_cast<uint8_t*>(d_eds) + first * eds_sq;
@@ -289,15 +251,10 @@ cel_status cel_dev_extend_batch(cel_ctx* ctx, const void* d_ods, uint32_t n, uin
                       d_status ? d_status + first : nullptr, static_cast<uint8_t*>(d_work) + plan.work_off[c],
                       (flags & CEL_FLAG_ORDER_CHECK) != 0, s);
     if (e != hipSuccess) break;
-    if ((e = hipEventRecord(ctx->ev_done[c], s)) != hipSuccess) break;
-    e = hipStreamWaitEvent(us, ctx->ev_done[c], 0);
+    if ((e = hipEventRecord(ctx->ev_committed[c], s)) != hipSuccess) break;
+    e = hipStreamWaitEvent(us, ctx->ev_committed[c], 0);
   }
   return e == hipSuccess ? CEL_OK : hip_fail(ctx, e, "extend batch");
-}
-
-static cel_status order_status(cel_ctx* ctx, int32_t st) {
-  if (st == CEL_EORDER) return fail(ctx, CEL_EORDER, "invalid push order: leaf namespaces must be non-decreasing");
-  return st;
 }
 
 // Device address of host memory the GPU can read directly (page-locked: cel_host_alloc,
@@ -325,107 +282,116 @@ static const uint8_t* mapped_host(const uint8_t* p) {
 //     itself (round 4: four copies into pageable memory, each a staging kernel and a host
 //     wait; round 5 first: one copy after the DAH launch).
 // The EDS download, if asked for, runs on a download stream after the column pass.
-static cel_status extend_one(cel_ctx* ctx, const uint8_t* ods, uint32_t k, uint8_t* eds_out, uint8_t* row_roots,
-                             uint8_t* col_roots, uint8_t* dah, int32_t* status_out, uint32_t flags) {
-  const size_t ods_b = (size_t)k * k * kShare, eds_b = 4 * ods_b, roots_b = (size_t)2 * k * kNode;
-  const size_t out_b = (2 * roots_b + 32 + 4 + 15) & ~(size_t)15;
-  hipError_t e = hipSuccess;
+// What the steps of one extend_one call share.
+struct OneSquare {
+  cel_ctx* ctx;
+  uint32_t k;
+  const uint8_t* ods;
+  uint8_t* eds_out;
+  bool order, parity_only;
+  // Page-locked output: EDS rows [r0, r1) < k go back as soon as the row pass wrote them,
+  // beside the later uploads, the column pass and the hashing (k=512 parity only 9.94 ->
+  // 8.20 ms, full EDS 12.3 -> 10.6-11.0 ms; k <= 256 -2 %: profiles/r5_eds_early_dl_ab.txt).
+  // A copy into pageable memory blocks this thread, so it stays after every launch.
+  bool early;
+  uint8_t *d_eds, *d_work;
+  hipStream_t s, d;  // compute, download
+};
+
+// The early download of EDS rows [r0, r1) < k, behind the row pass that `ev` marks here.
+static hipError_t one_download_top(const OneSquare& q, uint32_t r0, uint32_t r1, hipEvent_t ev) {
+  const hipError_t r = stream_after(q.d, ev, q.s);
+  return r != hipSuccess ? r : copy_back(q.eds_out, q.d_eds, ext::copy_back_rects(q.k, r0, r1, q.parity_only), q.d);
+}
+
+// The ODS into Q0 and its rows extended to Q1, by direct read, one DMA or four chunks; with
+// q.early the rows go back as they are done. *leaf0: the EDS rows whose leaves are hashed already.
+static hipError_t one_upload_rows(const OneSquare& q, uint32_t* leaf0) {
+  cel_ctx* ctx = q.ctx;
+  const uint32_t k = q.k;
+  const size_t rowb = (size_t)2 * k * kShare, odsrow = (size_t)k * kShare;
+  hipError_t r;
+  *leaf0 = 0;
+  if (k == 512 && mapped_host(q.ods)) {
+    // One k=512 block from page-locked memory: 128 MiB crosses PCIe in 4 row chunks on a
+    // copy stream, and each chunk's rows are extended and their leaves hashed on the
+    // compute stream while the next one crosses (3.58 -> 3.43 ms; at k = 256 the chunks
+    // cost more than they hide: profiles/r5_header_gf16_dma_ab.txt). The push-order check
+    // of a chunk's first row reads the row above, which the previous chunk brought.
+    const uint32_t rows = ext::upload_rows(k);
+    hipStream_t cp = ctx->dl[1];
+    if ((r = stream_after(cp, ctx->ev_start, q.s)) != hipSuccess) return r;
+    for (uint32_t c = 0; c < ext::kUp; c++) {
+      const uint32_t r0 = c * rows;
+      if ((r = hipMemcpy2DAsync(q.d_eds + r0 * rowb, rowb, q.ods + r0 * odsrow, odsrow, odsrow, rows,
+                                hipMemcpyHostToDevice, cp)) != hipSuccess ||
+          (r = stream_after(q.s, ctx->ev_up[c], cp)) != hipSuccess ||
+          (r = launch_extend_rows(q.d_eds, k, r0, r0 + rows, ctx->tables, q.s)) != hipSuccess ||
+          (q.early && (r = one_download_top(q, r0, r0 + rows, ctx->ev_rows[c])) != hipSuccess) ||
+          (r = launch_commit_leaves(q.d_eds, k, 1, q.d_work, q.order, r0, r0 + rows, c == 0, q.s)) != hipSuccess)
+        return r;
+    }
+    *leaf0 = k;
+    return hipSuccess;
+  }
   // The GF(2^8) row pass reads a page-locked ODS straight over PCIe (256-byte segments per
   // shard: the upload and the row transform are one launch). The GF(2^16) row kernel reads
   // 64-byte segments, which cross PCIe at ~39 GB/s, so at k = 256 / 512, and for pageable
   // memory, DMA copies put the ODS into Q0 and the rows are extended in place (k=512 header
   // 4.82 -> 3.43 ms, k=256 1.24 -> 1.03 ms, profiles/r5_header_gf16_dma_ab.txt).
-  const uint8_t* src = k <= kMaxGf8Width ? mapped_host(ods) : nullptr;
-  uint8_t* d_eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, eds_b, &e));
+  const uint8_t* src = k <= kMaxGf8Width ? mapped_host(q.ods) : nullptr;
+  if (!src && (r = hipMemcpy2DAsync(q.d_eds, rowb, q.ods, odsrow, odsrow, k, hipMemcpyHostToDevice, q.s)) != hipSuccess)
+    return r;
+  if ((r = launch_extend_rows(q.d_eds, k, 0, k, ctx->tables, q.s, src)) != hipSuccess) return r;
+  return q.early ? one_download_top(q, 0, k, ctx->ev_rows[0]) : hipSuccess;
+}
+
+// The EDS rows that have not gone back early, on the download stream, which the compute stream
+// then waits for. After every kernel is enqueued: a copy into pageable memory blocks the
+// calling thread.
+static hipError_t one_download_tail(const OneSquare& q) {
+  const uint32_t k = q.k;
+  const hipError_t r = copy_back(q.eds_out, q.d_eds, ext::copy_back_rects(k, q.early ? k : 0, 2 * k, q.parity_only), q.d);
+  return r != hipSuccess ? r : stream_after(q.s, q.ctx->ev_dl, q.d);
+}
+
+// The end of a host call: s drained, the result block in page-locked h handed out, the first
+// square's status that is not OK as the call's.
+static cel_status finish(cel_ctx* ctx, hipStream_t s, const ext::ResultBlock& rb, const uint8_t* h, uint8_t* row_roots,
+                         uint8_t* col_roots, uint8_t* dah, int32_t* status_out) {
+  const hipError_t e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_fail(ctx, e, "sync");
+  return order_status(ctx, rb.unpack(h, row_roots, col_roots, dah, status_out));
+}
+
+static cel_status extend_one(cel_ctx* ctx, const uint8_t* ods, uint32_t k, uint8_t* eds_out, uint8_t* row_roots,
+                             uint8_t* col_roots, uint8_t* dah, int32_t* status_out, uint32_t flags) {
+  const ext::ResultBlock rb(k, 1);
+  // rounded up to the 16-byte elements the DAH launch stores into the staging
+  const size_t out_b = (rb.bytes() + 15) & ~(size_t)15;
+  hipError_t e = hipSuccess;
+  uint8_t* d_eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, (size_t)4 * k * k * kShare, &e));
   uint8_t* d_work = static_cast<uint8_t*>(scratch(ctx, S_WORK, nmt_workspace_size(k, 1), &e));
   uint8_t* d_out = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, out_b, &e));
   uint8_t* h_out = static_cast<uint8_t*>(host_stage(ctx, out_b));
   if (!d_eds || !d_work || !d_out || !h_out) return fail(ctx, CEL_ENOMEM, "allocation failed");
   uint8_t* h_dev = const_cast<uint8_t*>(mapped_host(h_out));
   if (!h_dev) return fail(ctx, CEL_EDEVICE, "page-locked staging is not mapped for the device");
-  int32_t* d_st = reinterpret_cast<int32_t*>(d_out + 2 * roots_b + 32);
-  hipStream_t s = ctx->stream, d = ctx->dl[0];
-  auto enqueue = [&]() -> hipError_t {
-    hipError_t r;
-    const bool order = (flags & CEL_FLAG_ORDER_CHECK) != 0;
-    const size_t rowb = (size_t)2 * k * kShare, odsrow = (size_t)k * kShare;
-    uint32_t leaf0 = 0;  // EDS rows whose leaves are hashed already
-    // Page-locked output: EDS rows [r0, r1) < k go back as soon as the row pass wrote them,
-    // beside the later uploads, the column pass and the hashing (k=512 parity only 9.94 ->
-    // 8.20 ms, full EDS 12.3 -> 10.6-11.0 ms; k <= 256 -2 %: profiles/r5_eds_early_dl_ab.txt).
-    // A copy into pageable memory blocks this thread, so it stays after every launch.
-    const bool early = eds_out && mapped_host(eds_out);
-    auto dl_top = [&](uint32_t r0, uint32_t r1, int ev) -> hipError_t {
-      hipError_t q;
-      if ((q = hipEventRecord(ctx->ev_rs[ev], s)) != hipSuccess || (q = hipStreamWaitEvent(d, ctx->ev_rs[ev], 0)))
-        return q;
-      const size_t half = (size_t)k * kShare;
-      return (flags & CEL_FLAG_PARITY_ONLY)
-                 ? hipMemcpy2DAsync(eds_out + r0 * rowb + half, rowb, d_eds + r0 * rowb + half, rowb, half, r1 - r0,
-                                    hipMemcpyDeviceToHost, d)
-                 : hipMemcpyAsync(eds_out + r0 * rowb, d_eds + r0 * rowb, (r1 - r0) * rowb, hipMemcpyDeviceToHost, d);
-    };
-    if (k == 512 && mapped_host(ods)) {
-      // One k=512 block from page-locked memory: 128 MiB crosses PCIe in 4 row chunks on a
-      // copy stream, and each chunk's rows are extended and their leaves hashed on the
-      // compute stream while the next one crosses (3.58 -> 3.43 ms; at k = 256 the chunks
-      // cost more than they hide: profiles/r5_header_gf16_dma_ab.txt). The push-order check
-      // of a chunk's first row reads the row above, which the previous chunk brought.
-      constexpr uint32_t kUp = 4;
-      const uint32_t rows = k / kUp;
-      hipStream_t cp = ctx->dl[1];
-      if ((r = hipEventRecord(ctx->ev_start, s)) != hipSuccess || (r = hipStreamWaitEvent(cp, ctx->ev_start, 0)))
-        return r;
-      for (uint32_t c = 0; c < kUp; c++) {
-        const uint32_t r0 = c * rows;
-        if ((r = hipMemcpy2DAsync(d_eds + r0 * rowb, rowb, ods + r0 * odsrow, odsrow, odsrow, rows,
-                                  hipMemcpyHostToDevice, cp)) != hipSuccess ||
-            (r = hipEventRecord(ctx->ev_done[c], cp)) != hipSuccess ||
-            (r = hipStreamWaitEvent(s, ctx->ev_done[c], 0)) != hipSuccess ||
-            (r = launch_extend_rows(d_eds, k, r0, r0 + rows, ctx->tables, s)) != hipSuccess ||
-            (early && (r = dl_top(r0, r0 + rows, 1 + (int)c)) != hipSuccess) ||
-            (r = launch_commit_leaves(d_eds, k, 1, d_work, order, r0, r0 + rows, c == 0, s)) != hipSuccess)
-          return r;
-      }
-      leaf0 = k;
-    } else {
-      if (!src && (r = hipMemcpy2DAsync(d_eds, rowb, ods, odsrow, odsrow, k, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return r;
-      if ((r = launch_extend_rows(d_eds, k, 0, k, ctx->tables, s, src)) != hipSuccess) return r;
-      if (early && (r = dl_top(0, k, 1)) != hipSuccess) return r;
-    }
-    if ((r = launch_extend_cols(d_eds, k, 1, ctx->tables, s)) != hipSuccess) return r;
-    if (eds_out &&
-        ((r = hipEventRecord(ctx->ev_rs[0], s)) != hipSuccess || (r = hipStreamWaitEvent(d, ctx->ev_rs[0], 0))))
-      return r;
-    // the DAH launch writes every result into the page-locked staging itself
-    if ((r = launch_commit_leaves(d_eds, k, 1, d_work, order, leaf0, 2 * k, leaf0 == 0, s)) != hipSuccess ||
-        (r = launch_commit_trees(k, 1, d_out, d_out + roots_b, d_out + 2 * roots_b, d_st, d_work, s, h_dev,
-                                 (uint32_t)out_b)) != hipSuccess)
-      return r;
-    if (eds_out) {
-      // after every kernel is enqueued: a copy into pageable memory blocks the calling thread
-      const size_t half = (size_t)k * kShare;
-      r = early ? hipSuccess
-          : (flags & CEL_FLAG_PARITY_ONLY)
-              ? hipMemcpy2DAsync(eds_out + half, rowb, d_eds + half, rowb, half, k, hipMemcpyDeviceToHost, d)
-              : hipMemcpyAsync(eds_out, d_eds, k * rowb, hipMemcpyDeviceToHost, d);
-      if (r == hipSuccess)
-        r = hipMemcpyAsync(eds_out + k * rowb, d_eds + k * rowb, k * rowb, hipMemcpyDeviceToHost, d);
-      if (r == hipSuccess) r = hipEventRecord(ctx->ev_dl[0], d);
-      if (r == hipSuccess) r = hipStreamWaitEvent(s, ctx->ev_dl[0], 0);
-    }
-    return r;
-  };
-  if ((e = enqueue()) != hipSuccess) return hip_fail(ctx, e, "extend square");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  std::memcpy(row_roots, h_out, roots_b);
-  std::memcpy(col_roots, h_out + roots_b, roots_b);
-  std::memcpy(dah, h_out + 2 * roots_b, 32);
-  int32_t stv = 0;
-  std::memcpy(&stv, h_out + 2 * roots_b + 32, 4);
-  if (status_out) *status_out = stv;
-  return order_status(ctx, stv);
+  const bool order = (flags & CEL_FLAG_ORDER_CHECK) != 0, parity_only = (flags & CEL_FLAG_PARITY_ONLY) != 0;
+  const bool early = eds_out && mapped_host(eds_out);
+  const OneSquare q{ctx, k, ods, eds_out, order, parity_only, early, d_eds, d_work, ctx->stream, ctx->dl[0]};
+  uint32_t leaf0 = 0;
+  if ((e = one_upload_rows(q, &leaf0)) != hipSuccess ||
+      (e = launch_extend_cols(d_eds, k, 1, ctx->tables, q.s)) != hipSuccess ||
+      (eds_out && (e = stream_after(q.d, ctx->ev_cols, q.s)) != hipSuccess) ||
+      (e = launch_commit_leaves(d_eds, k, 1, d_work, q.order, leaf0, 2 * k, leaf0 == 0, q.s)) != hipSuccess ||
+      // the DAH launch writes every result into the page-locked staging itself
+      (e = launch_commit_trees(k, 1, d_out + rb.row_roots(), d_out + rb.col_roots(), d_out + rb.dah(),
+                               reinterpret_cast<int32_t*>(d_out + rb.status()), d_work, q.s, h_dev, (uint32_t)out_b)) !=
+          hipSuccess ||
+      (eds_out && (e = one_download_tail(q)) != hipSuccess))
+    return hip_fail(ctx, e, "extend square");
+  return finish(ctx, q.s, rb, h_out, row_roots, col_roots, dah, status_out);
 }
 
 cel_status cel_extend_batch(cel_ctx* ctx, const uint8_t* ods, uint32_t n, uint32_t k, uint32_t share_size,
@@ -438,97 +404,64 @@ cel_status cel_extend_batch(cel_ctx* ctx, const uint8_t* ods, uint32_t n, uint32
   if (st) return st;
   DeviceGuard g(ctx->device);
   if (n == 1 && k >= 32) return extend_one(ctx, ods, k, eds_out, row_roots, col_roots, dah, status_out, flags);
-  const size_t ods_b = (size_t)n * k * k * kShare, eds_b = 4 * ods_b;
-  const size_t roots_b = (size_t)n * 2 * k * kNode;
   hipError_t e = hipSuccess;
   // Chunked host pipeline: chunk c goes through upload (ODS into Q0) -> extension ->
-  // commit -> download on internal stream c % kPipe, so the PCIe copies of one chunk
+  // commit -> download on its internal stream, so the PCIe copies of one chunk
   // overlap the kernels and copies of the others (the copies dominate: 40 MiB of
   // PCIe traffic per k=128 square against ~50 us of kernels). Host buffers from
   // cel_host_alloc (pinned) make every copy asynchronous.
-  const uint32_t nc = std::min<uint32_t>(n, kHostChunks);
-  const uint32_t chunk = (n + nc - 1) / nc;
-  const uint32_t nchunks = (n + chunk - 1) / chunk;
-  const uint32_t nstreams = std::min<uint32_t>(nchunks, cel_ctx::kPipe);
-  const size_t ws = nmt_workspace_size(k, chunk);
-  uint8_t* d_eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, eds_b, &e));
-  if (!d_eds) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  uint8_t* d_work = static_cast<uint8_t*>(scratch(ctx, S_WORK, nstreams * ws, &e));
-  if (!d_work) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  const size_t out_b = 2 * roots_b + (size_t)n * 32 + (size_t)n * 4;
-  uint8_t* d_out = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, out_b, &e));
-  if (!d_out) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  uint8_t* h_out = static_cast<uint8_t*>(host_stage(ctx, out_b));
-  if (!h_out) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  uint8_t* d_rr = d_out;
-  uint8_t* d_cr = d_out + roots_b;
-  uint8_t* d_dah = d_out + 2 * roots_b;
-  int32_t* d_st = reinterpret_cast<int32_t*>(d_out + 2 * roots_b + (size_t)n * 32);
-  std::vector<int32_t> stv(n);
-  hipStream_t s = ctx->stream;
+  const ext::HostPlan plan = ext::host_plan(n);
+  const ext::ResultBlock rb(k, n);
   const uint64_t ods_sq = (uint64_t)k * k * kShare, eds_sq = 4 * ods_sq, roots_sq = (uint64_t)2 * k * kNode;
+  const size_t ws = nmt_workspace_size(k, plan.chunk);
+  uint8_t* d_eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, n * eds_sq, &e));
+  if (!d_eds) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+  uint8_t* d_work = static_cast<uint8_t*>(scratch(ctx, S_WORK, plan.nslots * ws, &e));
+  if (!d_work) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+  uint8_t* d_out = static_cast<uint8_t*>(scratch(ctx, S_ROOTS, rb.bytes(), &e));
+  if (!d_out) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+  uint8_t* h_out = static_cast<uint8_t*>(host_stage(ctx, rb.bytes()));
+  if (!h_out) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
+  int32_t* d_st = reinterpret_cast<int32_t*>(d_out + rb.status());
+  hipStream_t s = ctx->stream;
   if ((e = hipEventRecord(ctx->ev_start, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  for (uint32_t c = 0; c < nchunks; c++) {
-    const uint32_t first = c * chunk, cnt = (first + chunk <= n) ? chunk : n - first;
-    hipStream_t cs = ctx->sub[c % cel_ctx::kPipe];
+  for (uint32_t c = 0; c < plan.nchunks; c++) {
+    const uint32_t first = plan.first(c), cnt = plan.cnt(c);
+    hipStream_t cs = ctx->sub[plan.slot(c)];
     uint8_t* eds_c = d_eds + first * eds_sq;
     if ((e = hipStreamWaitEvent(cs, ctx->ev_start, 0)) != hipSuccess ||
         (e = place_ods(ods + first * ods_sq, cnt, k, eds_c, cs)) != hipSuccess ||
         (e = launch_extend(nullptr, eds_c, k, cnt, ctx->tables, cs)) != hipSuccess ||
-        (e = hipEventRecord(ctx->ev_rs[c % cel_ctx::kChunks], cs)) != hipSuccess ||
-        (e = launch_commit(eds_c, k, cnt, d_rr + first * roots_sq, d_cr + first * roots_sq, d_dah + first * 32,
-                           d_st + first, d_work + (c % cel_ctx::kPipe) * ws, (flags & CEL_FLAG_ORDER_CHECK) != 0,
-                           cs)) != hipSuccess)
+        (e = hipEventRecord(ctx->ev_extended[c], cs)) != hipSuccess ||
+        (e = launch_commit(eds_c, k, cnt, d_out + rb.row_roots() + first * roots_sq,
+                           d_out + rb.col_roots() + first * roots_sq, d_out + rb.dah() + first * 32, d_st + first,
+                           d_work + plan.slot(c) * ws, (flags & CEL_FLAG_ORDER_CHECK) != 0, cs)) != hipSuccess)
       return hip_fail(ctx, e, "extend batch");
   }
   // Downloads after every chunk is enqueued: a copy into pageable memory blocks the
   // calling thread, and the later chunks' kernels run meanwhile. A chunk's EDS goes back
   // on the download stream as soon as its extension is done, beside its own hashing.
-  for (uint32_t c = 0; c < nchunks; c++) {
-    const uint32_t first = c * chunk, cnt = (first + chunk <= n) ? chunk : n - first;
-    hipStream_t cs = ctx->sub[c % cel_ctx::kPipe];
-    uint8_t* eds_c = d_eds + first * eds_sq;
-    // one download stream, chunks in order: one DMA stream at the link's rate (four
-    // concurrent ones measured 1.75K -> 1.0K squares/s on the parity-only copies)
-    hipStream_t ds = ctx->dl[0];
-    if (eds_out && (e = hipStreamWaitEvent(ds, ctx->ev_rs[c % cel_ctx::kChunks], 0)) != hipSuccess)
-      return hip_fail(ctx, e, "event");
+  // One download stream, chunks in order: one DMA stream at the link's rate (four
+  // concurrent ones measured 1.75K -> 1.0K squares/s on the parity-only copies).
+  hipStream_t ds = ctx->dl[0];
+  for (uint32_t c = 0; c < plan.nchunks; c++) {
+    const uint32_t first = plan.first(c), cnt = plan.cnt(c);
+    if (eds_out && (e = hipStreamWaitEvent(ds, ctx->ev_extended[c], 0)) != hipSuccess) return hip_fail(ctx, e, "event");
     if (eds_out && (flags & CEL_FLAG_PARITY_ONLY)) {
-      // Q1 (the right half of rows 0..k-1, one strided copy) then Q2|Q3 (contiguous)
-      const size_t half = (size_t)k * kShare;
-      for (uint32_t i = 0; i < cnt && e == hipSuccess; i++) {
-        uint8_t* h = eds_out + (first + i) * eds_sq;
-        const uint8_t* d = eds_c + i * eds_sq;
-        if ((e = hipMemcpy2DAsync(h + half, 2 * half, d + half, 2 * half, half, k, hipMemcpyDeviceToHost, ds)) ==
-            hipSuccess)
-          e = hipMemcpyAsync(h + eds_sq / 2, d + eds_sq / 2, eds_sq / 2, hipMemcpyDeviceToHost, ds);
-      }
-      if (e != hipSuccess) return hip_fail(ctx, e, "D2H");
-    } else if (eds_out && (e = hipMemcpyAsync(eds_out + first * eds_sq, eds_c, cnt * eds_sq, hipMemcpyDeviceToHost,
-                                              ds)) != hipSuccess) {
-      return hip_fail(ctx, e, "D2H");
+      const ext::Rects parity = ext::copy_back_rects(k, 0, 2 * k, true);
+      for (uint32_t i = first; i < first + cnt && e == hipSuccess; i++)
+        e = copy_back(eds_out + i * eds_sq, d_eds + i * eds_sq, parity, ds);
+    } else if (eds_out) {  // a chunk's whole squares lie back to back on both sides: one copy
+      e = hipMemcpyAsync(eds_out + first * eds_sq, d_eds + first * eds_sq, cnt * eds_sq, hipMemcpyDeviceToHost, ds);
     }
-    if ((e = hipEventRecord(ctx->ev_done[c % cel_ctx::kChunks], cs)) != hipSuccess ||
-        (e = hipStreamWaitEvent(s, ctx->ev_done[c % cel_ctx::kChunks], 0)) != hipSuccess)
-      return hip_fail(ctx, e, "event");
+    if (e != hipSuccess) return hip_fail(ctx, e, "D2H");
+    if ((e = stream_after(s, ctx->ev_committed[c], ctx->sub[plan.slot(c)])) != hipSuccess) return hip_fail(ctx, e, "event");
   }
-  if (eds_out && ((e = hipEventRecord(ctx->ev_dl[0], ctx->dl[0])) != hipSuccess ||
-                  (e = hipStreamWaitEvent(s, ctx->ev_dl[0], 0)) != hipSuccess))
-    return hip_fail(ctx, e, "event");
+  if (eds_out && (e = stream_after(s, ctx->ev_dl, ds)) != hipSuccess) return hip_fail(ctx, e, "event");
   // every result in one copy into page-locked staging (one D2H into pageable memory costs
   // a staging kernel and a host wait each: four of them per chunk were ~25 us apiece)
-  if ((e = hipMemcpyAsync(h_out, d_out, out_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  std::memcpy(row_roots, h_out, roots_b);
-  std::memcpy(col_roots, h_out + roots_b, roots_b);
-  std::memcpy(dah, h_out + 2 * roots_b, (size_t)n * 32);
-  std::memcpy(stv.data(), h_out + 2 * roots_b + (size_t)n * 32, (size_t)n * 4);
-  cel_status worst = CEL_OK;
-  for (uint32_t i = 0; i < n; i++) {
-    if (status_out) status_out[i] = stv[i];
-    if (stv[i] != CEL_OK && worst == CEL_OK) worst = stv[i];
-  }
-  return order_status(ctx, worst);
+  if ((e = hipMemcpyAsync(h_out, d_out, rb.bytes(), hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
+  return finish(ctx, s, rb, h_out, row_roots, col_roots, dah, status_out);
 }
 
 cel_status cel_extend_shares(cel_ctx* ctx, const uint8_t* shares, uint32_t n_shares, uint32_t share_size,

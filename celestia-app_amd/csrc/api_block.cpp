@@ -54,31 +54,20 @@ cel_status check_layout(cel_ctx* ctx, const cel_square_segment* segs, uint32_t n
 
 // Uploads the plan of a checked layout (the segments with their BLOB offsets lowered by sub,
 // the share -> segment table, the compact shares) into scratch slot S_SQ through the
-// page-locked sq_stage, and enqueues k_square_build on s. d_txs + (off - sub) is a blob's
+// ctx's staged upload square_up, and enqueues k_square_build on s. d_txs + (off - sub) is a blob's
 // first byte. ctx->mu held, device current.
 cel_status enqueue_square(cel_ctx* ctx, const uint8_t* d_txs, uint64_t sub, const cel_square_segment* segs,
                           uint32_t nseg, const uint8_t* compact, uint32_t ncompact, uint32_t k, uint8_t* d_eds,
                           hipStream_t s) {
   hipError_t e;
-  if (!ctx->ev_sq_up && (e = hipEventCreateWithFlags(&ctx->ev_sq_up, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  if (!ctx->ev_sq_done && (e = hipEventCreateWithFlags(&ctx->ev_sq_done, hipEventDisableTiming)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  if (ctx->sq_pending && (e = hipEventSynchronize(ctx->ev_sq_up)) != hipSuccess) return hip_fail(ctx, e, "plan upload");
   const size_t seg_b = align256((size_t)nseg * sizeof(cel_square_segment));
   const size_t tab_b = align256((size_t)k * k * 4);
   const size_t bytes = seg_b + tab_b + (size_t)ncompact * kShare;
-  if (ctx->sq_stage_size < bytes) {
-    if (ctx->sq_stage) (void)hipHostFree(ctx->sq_stage);
-    ctx->sq_stage = nullptr;
-    ctx->sq_stage_size = 0;
-    if (hipHostMalloc(&ctx->sq_stage, bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->sq_stage = nullptr;
-      return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-    }
-    ctx->sq_stage_size = bytes;
-  }
-  uint8_t* st = static_cast<uint8_t*>(ctx->sq_stage);
+  if (!ctx->ev_sq_done && (e = hipEventCreateWithFlags(&ctx->ev_sq_done, hipEventDisableTiming)) != hipSuccess)
+    return hip_fail(ctx, e, "event");
+  cel_status status = CEL_OK;
+  uint8_t* st = static_cast<uint8_t*>(stage_acquire(ctx, ctx->square_up, bytes, &status));
+  if (!st) return status;
   cel_square_segment* hs = reinterpret_cast<cel_square_segment*>(st);
   uint32_t* tab = reinterpret_cast<uint32_t*>(st + seg_b);
   for (uint32_t i = 0; i < nseg; i++) {
@@ -91,10 +80,10 @@ cel_status enqueue_square(cel_ctx* ctx, const uint8_t* d_txs, uint64_t sub, cons
   uint8_t* d_plan = static_cast<uint8_t*>(scratch(ctx, S_SQ, bytes, &e));
   if (!d_plan) return fail(ctx, CEL_ENOMEM, "device allocation failed");
   // the previous build (perhaps on another stream) reads the device plan until ev_sq_done
-  if (ctx->sq_pending && (e = hipStreamWaitEvent(s, ctx->ev_sq_done, 0)) != hipSuccess) return hip_fail(ctx, e, "event");
+  if (ctx->sq_built && (e = hipStreamWaitEvent(s, ctx->ev_sq_done, 0)) != hipSuccess) return hip_fail(ctx, e, "event");
   if ((e = hipMemcpyAsync(d_plan, st, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(ctx, e, "H2D");
-  if ((e = hipEventRecord(ctx->ev_sq_up, s)) != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->sq_pending = true;
+  if ((status = stage_uploaded(ctx, ctx->square_up, s)) != CEL_OK) return status;
+  ctx->sq_built = true;
   e = launch_square_build(d_txs, reinterpret_cast<const cel_square_segment*>(d_plan),
                           reinterpret_cast<const uint32_t*>(d_plan + seg_b), d_plan + seg_b + tab_b, d_eds, k, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "square build");
@@ -147,7 +136,8 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
   const uint32_t k = L.k;
   *k_out = k;
   if (n_commit) *n_commit = (uint32_t)all.size();
-  const size_t ods_b = (size_t)k * k * kShare, eds_b = 4 * ods_b, roots_b = (size_t)2 * k * kNode;
+  const size_t eds_b = (size_t)4 * k * k * kShare;
+  const ext::ResultBlock rb(k, 1);
   if (eds_out && eds_cap < eds_b)
     return fail(ctx, CEL_EINVAL,
                 "EDS output holds " + std::to_string(eds_cap) + " bytes, the square needs " + std::to_string(eds_b));
@@ -181,7 +171,8 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream, d = ctx->dl[0];
   hipError_t e = hipSuccess;
-  const size_t out_b = align256(2 * roots_b + 32 + 4), res_b = out_b + (size_t)nb * 32;
+  // the commitments follow the result block on a 256-byte boundary
+  const size_t out_b = align256(rb.bytes()), res_b = out_b + (size_t)nb * 32;
   const size_t nmt_b = align256(nmt_workspace_size(k, 1));
   const bool direct = up_b && page_locked(txs);
   // + 8: the last dword a lane may touch starts inside the data; keep it inside the buffer
@@ -193,7 +184,7 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
   if (!d_in || !d_eds || !d_work || !d_out) return fail(ctx, CEL_ENOMEM, "device allocation failed");
   uint8_t* h_out = static_cast<uint8_t*>(host_stage(ctx, res_b + (direct ? 0 : up_b)));
   if (!h_out) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  int32_t* d_st = reinterpret_cast<int32_t*>(d_out + 2 * roots_b + 32);
+  int32_t* d_st = reinterpret_cast<int32_t*>(d_out + rb.status());
 
   if (up_b) {
     const uint8_t* src = txs + lo;
@@ -207,10 +198,8 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
                            L.compact.data(), (uint32_t)(L.compact.size() / kShare), k, d_eds, s)) != CEL_OK)
     return st;
   if ((e = launch_extend(nullptr, d_eds, k, 1, ctx->tables, s)) != hipSuccess) return hip_fail(ctx, e, "extend square");
-  if (eds_out && ((e = hipEventRecord(ctx->ev_rs[0], s)) != hipSuccess ||
-                  (e = hipStreamWaitEvent(d, ctx->ev_rs[0], 0)) != hipSuccess))
-    return hip_fail(ctx, e, "event");
-  if ((e = launch_commit(d_eds, k, 1, d_out, d_out + roots_b, d_out + 2 * roots_b, d_st, d_work,
+  if (eds_out && (e = stream_after(d, ctx->ev_cols, s)) != hipSuccess) return hip_fail(ctx, e, "event");
+  if ((e = launch_commit(d_eds, k, 1, d_out + rb.row_roots(), d_out + rb.col_roots(), d_out + rb.dah(), d_st, d_work,
                          (flags & CEL_FLAG_ORDER_CHECK) != 0, s)) != hipSuccess)
     return hip_fail(ctx, e, "commit square");
   if (nb && (st = commit_enqueue(ctx, d_in, 0, offs.data(), items.data(), nb, subtree_root_threshold, d_out + out_b,
@@ -220,24 +209,13 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
   if ((e = hipMemcpyAsync(h_out, d_out, res_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
   if (eds_out) {
     // after every launch is enqueued: a copy into pageable memory blocks the calling thread
-    const size_t rowb = (size_t)2 * k * kShare, half = (size_t)k * kShare;
-    e = (flags & CEL_FLAG_PARITY_ONLY)
-            ? hipMemcpy2DAsync(eds_out + half, rowb, d_eds + half, rowb, half, k, hipMemcpyDeviceToHost, d)
-            : hipMemcpyAsync(eds_out, d_eds, k * rowb, hipMemcpyDeviceToHost, d);
-    if (e == hipSuccess) e = hipMemcpyAsync(eds_out + k * rowb, d_eds + k * rowb, k * rowb, hipMemcpyDeviceToHost, d);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_dl[0], d);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s, ctx->ev_dl[0], 0);
+    e = copy_back(eds_out, d_eds, ext::copy_back_rects(k, 0, 2 * k, (flags & CEL_FLAG_PARITY_ONLY) != 0), d);
+    if (e == hipSuccess) e = stream_after(s, ctx->ev_dl, d);
     if (e != hipSuccess) return hip_fail(ctx, e, "D2H");
   }
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  std::memcpy(row_roots, h_out, roots_b);
-  std::memcpy(col_roots, h_out + roots_b, roots_b);
-  std::memcpy(dah, h_out + 2 * roots_b, 32);
   if (nb) std::memcpy(commitments, h_out + out_b, (size_t)nb * 32);
-  int32_t stv = 0;
-  std::memcpy(&stv, h_out + 2 * roots_b + 32, 4);
-  if (stv == CEL_EORDER) return fail(ctx, CEL_EORDER, "invalid push order: leaf namespaces must be non-decreasing");
-  return stv;
+  return order_status(ctx, rb.unpack(h_out, row_roots, col_roots, dah, nullptr));
 }
 
 }  // extern "C"

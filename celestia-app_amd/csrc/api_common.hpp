@@ -1,7 +1,7 @@
 // Shared helpers of the C-ABI host layer (every api_*.cpp): error reporting with the
-// reference's messages, grow-only device scratch and page-locked staging per ctx, the plan
-// buffer's upload rule, device selection, argument checks of a square, and the entry points
-// one api file lends another (blob commitments, the repair with the ctx lock held).
+// reference's messages, grow-only device scratch and page-locked staging per ctx, the staged
+// uploads' rule, the EDS copy-back, device selection, argument checks of a square, and the
+// entry points one api file lends another (blob commitments, the repair with the ctx lock held).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,44 +52,77 @@ inline void* host_stage(cel_ctx* ctx, size_t bytes) {
   return ctx->hstage;
 }
 
-// The ctx's page-locked plan buffer with room for `bytes`, once its last upload has left it
-// (the ev_plan rule of cel_internal.hpp). nullptr with the status in *st. A caller that
-// uploads from the buffer calls plan_uploaded behind the copy, unless it waits for the stream
-// itself before it returns (the namespace plan).
-inline void* plan_stage(cel_ctx* ctx, size_t bytes, cel_status* st) {
+// A staged upload's buffer with room for `bytes`, once its last upload has left it (the
+// StagedUpload rule of cel_internal.hpp). nullptr with the status in *st. A caller that uploads
+// from the buffer calls stage_uploaded behind the copy, unless it waits for the stream itself
+// before it returns (the namespace plan).
+inline void* stage_acquire(cel_ctx* ctx, StagedUpload& u, size_t bytes, cel_status* st) {
   if (bytes == 0) bytes = 256;  // never nullptr on success
   hipError_t e;
-  if (!ctx->ev_plan && (e = hipEventCreateWithFlags(&ctx->ev_plan, hipEventDisableTiming)) != hipSuccess) {
+  if (!u.ev && (e = hipEventCreateWithFlags(&u.ev, hipEventDisableTiming)) != hipSuccess) {
     *st = hip_fail(ctx, e, "event");
     return nullptr;
   }
-  if (ctx->plan_pending) {
-    if ((e = hipEventSynchronize(ctx->ev_plan)) != hipSuccess) {
+  if (u.pending) {
+    if ((e = hipEventSynchronize(u.ev)) != hipSuccess) {
       *st = hip_fail(ctx, e, "plan upload");
       return nullptr;
     }
-    ctx->plan_pending = false;
+    u.pending = false;
   }
-  if (ctx->plan_stage_size < bytes) {
-    if (ctx->plan_stage) (void)hipHostFree(ctx->plan_stage);
-    ctx->plan_stage = nullptr;
-    ctx->plan_stage_size = 0;
-    if (hipHostMalloc(&ctx->plan_stage, bytes, hipHostMallocDefault) != hipSuccess) {
-      ctx->plan_stage = nullptr;
+  if (u.size < bytes) {
+    if (u.buf) (void)hipHostFree(u.buf);
+    u.buf = nullptr;
+    u.size = 0;
+    if (hipHostMalloc(&u.buf, bytes, hipHostMallocDefault) != hipSuccess) {
+      u.buf = nullptr;
       *st = fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
       return nullptr;
     }
-    ctx->plan_stage_size = bytes;
+    u.size = bytes;
   }
-  return ctx->plan_stage;
+  return u.buf;
 }
 
-// After the copy out of the plan buffer has been enqueued on s: the next plan_stage waits for it.
-inline cel_status plan_uploaded(cel_ctx* ctx, hipStream_t s) {
-  const hipError_t e = hipEventRecord(ctx->ev_plan, s);
+// After the copy out of the buffer has been enqueued on s: the next stage_acquire waits for it.
+inline cel_status stage_uploaded(cel_ctx* ctx, StagedUpload& u, hipStream_t s) {
+  const hipError_t e = hipEventRecord(u.ev, s);
   if (e != hipSuccess) return hip_fail(ctx, e, "event");
-  ctx->plan_pending = true;
+  u.pending = true;
   return CEL_OK;
+}
+
+// The ctx's plan buffer under that rule.
+inline void* plan_stage(cel_ctx* ctx, size_t bytes, cel_status* st) { return stage_acquire(ctx, ctx->plan_up, bytes, st); }
+inline cel_status plan_uploaded(cel_ctx* ctx, hipStream_t s) { return stage_uploaded(ctx, ctx->plan_up, s); }
+
+// A square's push-order status as the call's result, with the reference's message.
+constexpr const char* kOrderMessage = "invalid push order: leaf namespaces must be non-decreasing";
+inline cel_status order_status(cel_ctx* ctx, int32_t st) {
+  return st == CEL_EORDER ? fail(ctx, CEL_EORDER, kOrderMessage) : (cel_status)st;
+}
+
+// The rectangles of an EDS copy-back (ext::copy_back_rects) enqueued on s, in order. One that is
+// contiguous on both sides goes as hipMemcpyAsync, a strided one as hipMemcpy2DAsync: the DMA
+// engines treat the two calls differently, and the paths were measured with these. always_2d:
+// every rectangle as a 2-D copy (the shard plan's slabs, also the one rank's whole square).
+inline hipError_t copy_back(uint8_t* host, const uint8_t* dev, const ext::Rects& rs, hipStream_t s,
+                            bool always_2d = false) {
+  hipError_t e = hipSuccess;
+  for (uint32_t i = 0; i < rs.n && e == hipSuccess; i++) {
+    const ext::Rect& r = rs.r[i];
+    e = r.contiguous() && !always_2d
+            ? hipMemcpyAsync(host + r.dst_off, dev + r.src_off, r.width * r.rows, hipMemcpyDeviceToHost, s)
+            : hipMemcpy2DAsync(host + r.dst_off, r.dst_pitch, dev + r.src_off, r.src_pitch, r.width, r.rows,
+                               hipMemcpyDeviceToHost, s);
+  }
+  return e;
+}
+
+// `to` goes on only behind what `from` holds now: ev recorded on from, waited for on to.
+inline hipError_t stream_after(hipStream_t to, hipEvent_t ev, hipStream_t from) {
+  const hipError_t e = hipEventRecord(ev, from);
+  return e == hipSuccess ? hipStreamWaitEvent(to, ev, 0) : e;
 }
 
 inline bool is_pow2(uint64_t n) { return n && !(n & (n - 1)); }
@@ -131,8 +164,8 @@ cel_status commit_check_blob(cel_ctx* ctx, uint32_t i, uint64_t len, uint32_t sh
 // Workspace for any plan of nblobs blobs with total_shares shares.
 size_t commit_workspace_bound(uint64_t total_shares, uint32_t nblobs);
 // Plans nb blobs whose bytes lie in d_data back to back from base_off on (offs == nullptr) or
-// at byte offsets offs[i]; uploads the plan into d_work's head (through ctx->plan_stage, under
-// its ev_plan rule) and enqueues the kernels on s: 32 bytes per blob into d_out.
+// at byte offsets offs[i]; uploads the plan into d_work's head (through plan_stage, under
+// its rule) and enqueues the kernels on s: 32 bytes per blob into d_out.
 cel_status commit_enqueue(cel_ctx* ctx, const uint8_t* d_data, uint64_t base_off, const uint64_t* offs,
                           const CommitItem* items, uint32_t nb, uint32_t threshold, uint8_t* d_out, void* d_work,
                           hipStream_t s);

@@ -112,7 +112,7 @@ struct cel_shard_plan {
     uint8_t* gathered = nullptr;  // [N][2k + w + 1][96] (the record block itself when local)
     uint8_t* work = nullptr;
     // rank 0: the finish's outputs, contiguous so one copy brings them back
-    uint8_t* out = nullptr;  // row roots [2k][90] | col roots [2k][90] | dah [32] | status int32
+    uint8_t* out = nullptr;  // results(): row roots [2k][90] | col roots [2k][90] | dah [32] | status int32
     hipEvent_t ev_rows = nullptr, ev_exch = nullptr, ev_cols = nullptr;
   };
   uint32_t ngpu = 0, k = 0, w = 0, flags = 0;
@@ -128,7 +128,8 @@ struct cel_shard_plan {
   std::mutex mu;
 
   size_t pack_bytes() const { return (size_t)(2 * k + w + 1) * CEL_NODE_RECORD; }
-  size_t out_bytes() const { return (size_t)4 * k * kNode + 32 + 4; }
+  ext::ResultBlock results() const { return ext::ResultBlock(k, 1); }
+  size_t out_bytes() const { return results().bytes(); }
   uint64_t block_bytes() const { return (uint64_t)(k / ngpu) * w * kShare; }  // one all-to-all block
 };
 
@@ -457,9 +458,9 @@ cel_status cel_shard_plan_run(cel_shard_plan* p) {
   {
     DeviceGuard g(r0.device);
     uint8_t* o = r0.out;
-    e = launch_shard_finish(reinterpret_cast<const uint32_t*>(r0.gathered), k, N, o, o + 2 * k * kNode,
-                            o + 4 * k * kNode, reinterpret_cast<int32_t*>(o + 4 * k * kNode + 32), r0.work, order,
-                            r0.s);
+    const ext::ResultBlock rb = p->results();
+    e = launch_shard_finish(reinterpret_cast<const uint32_t*>(r0.gathered), k, N, o + rb.row_roots(), o + rb.col_roots(),
+                            o + rb.dah(), reinterpret_cast<int32_t*>(o + rb.status()), r0.work, order, r0.s);
     if (e == hipSuccess) e = hipEventRecord(p->ev_fin, r0.s);
     if (e != hipSuccess) return plan_hip(p, e, "shard finish");
   }
@@ -476,23 +477,16 @@ cel_status cel_shard_plan_wait(cel_shard_plan* p, uint8_t* eds_out, uint8_t* row
   if (!p) return CEL_EINVAL;
   std::lock_guard<std::mutex> lock(p->mu);
   if (!p->ran) return plan_fail(p, CEL_EINVAL, "shard plan: nothing has run");
-  const uint32_t k = p->k, W = 2 * k, w = p->w;
+  const uint32_t k = p->k, w = p->w;
   hipError_t e = hipSuccess;
   if (eds_out) {
-    const size_t rowb = (size_t)W * kShare;
     for (uint32_t i = 0; i < p->ngpu && e == hipSuccess; i++) {
       auto& rk = p->r[i];
       DeviceGuard g(rk.device);
-      const uint32_t c0 = i * w, c1 = c0 + w;
-      // top half: columns [max(c0, k), c1) unless Q0 is skipped; bottom half: all w columns
-      const uint32_t t0 = (p->flags & CEL_FLAG_PARITY_ONLY) ? std::max(c0, k) : c0;
-      if (t0 < c1)
-        e = hipMemcpy2DAsync(eds_out + (size_t)t0 * kShare, rowb, rk.slab + (size_t)(t0 - c0) * kShare,
-                             (size_t)w * kShare, (size_t)(c1 - t0) * kShare, k, hipMemcpyDeviceToHost, rk.s);
-      if (e == hipSuccess)
-        e = hipMemcpy2DAsync(eds_out + (size_t)k * rowb + (size_t)c0 * kShare, rowb,
-                             rk.slab + (size_t)k * w * kShare, (size_t)w * kShare, (size_t)w * kShare, k,
-                             hipMemcpyDeviceToHost, rk.s);
+      // the rank's columns [i w, (i + 1) w) of every row, every rectangle as a 2-D copy (also
+      // the one rank's, whose slab is the whole square)
+      e = copy_back(eds_out, rk.slab, ext::copy_back_rects(k, 0, 2 * k, (p->flags & CEL_FLAG_PARITY_ONLY) != 0, i * w, w),
+                    rk.s, true);
     }
     if (e != hipSuccess) return plan_hip(p, e, "shard plan download");
   }
@@ -506,13 +500,8 @@ cel_status cel_shard_plan_wait(cel_shard_plan* p, uint8_t* eds_out, uint8_t* row
     DeviceGuard g(rk.device);
     if ((e = hipStreamSynchronize(rk.s)) != hipSuccess) return plan_hip(p, e, "shard plan sync");
   }
-  const uint8_t* h = static_cast<const uint8_t*>(p->host_out);
-  if (row_roots) std::memcpy(row_roots, h, (size_t)W * kNode);
-  if (col_roots) std::memcpy(col_roots, h + (size_t)W * kNode, (size_t)W * kNode);
-  if (dah) std::memcpy(dah, h + (size_t)2 * W * kNode, 32);
-  int32_t st = 0;
-  std::memcpy(&st, h + (size_t)2 * W * kNode + 32, 4);
-  if (st == CEL_EORDER) return plan_fail(p, CEL_EORDER, "invalid push order: leaf namespaces must be non-decreasing");
+  const int32_t st = p->results().unpack(p->host_out, row_roots, col_roots, dah, nullptr);
+  if (st == CEL_EORDER) return plan_fail(p, CEL_EORDER, kOrderMessage);
   return st ? plan_fail(p, st, "shard plan: device status " + std::to_string(st)) : CEL_OK;
 }
 

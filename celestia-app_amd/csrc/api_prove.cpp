@@ -47,7 +47,7 @@ cel_status offsets(uint32_t k, uint32_t n, const int32_t* starts, const int32_t*
   return CEL_OK;
 }
 
-// The request table of a batch through the ctx's page-locked plan buffer (under its ev_plan
+// The request table of a batch through the ctx's page-locked plan buffer (under its staged-upload
 // rule, as verify_enqueue does) into d_work, then the kernel. ctx->mu held, device current.
 cel_status prove_enqueue(cel_ctx* ctx, const uint8_t* d_eds, const void* d_index, uint32_t k, uint32_t n,
                          const uint8_t* axes, const uint32_t* index, const int32_t* starts, const int32_t* ends,

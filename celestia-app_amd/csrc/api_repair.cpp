@@ -617,13 +617,13 @@ static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs
   carved(carve_stage, ctx->hstage, *b);
   b->slot = 0;
   b->solves = 0;
-  // the side stream and the events are the batch pipeline's (the ctx lock is held)
+  // the side stream is the batch pipeline's (the ctx lock is held); the events are the repair's own
   b->main = ctx->stream;
   b->side = ctx->sub[0];
-  b->ev_main = ctx->ev_rs[0];
-  b->ev_side[0] = ctx->ev_rs[1];
-  b->ev_side[1] = ctx->ev_rs[2];
-  b->ev_done = ctx->ev_rs[3];
+  b->ev_main = ctx->ev_repair_main;
+  b->ev_side[0] = ctx->ev_repair_side[0];
+  b->ev_side[1] = ctx->ev_repair_side[1];
+  b->ev_done = ctx->ev_repair_done;
   // no stale record of an earlier call may gate this one: both streams start from here
   if ((e = hipEventRecord(b->ev_side[0], b->side)) != hipSuccess || (e = hipEventRecord(b->ev_side[1], b->side)) != hipSuccess)
     return hip_fail(ctx, e, "event");

@@ -3,14 +3,7 @@
 // gathered records; collectives are the caller's (RCCL). Split from api.cpp.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <climits>
-#include <cstdlib>
-#include <cstdio>
-#include <cstring>
-#include <memory>
 #include <string>
-#include <vector>
 
 #include "api_common.hpp"
 #include "cel_internal.hpp"

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../../include/celestia_eds.h"
+#include "extend_plan.hpp"
 
 namespace cel {
 
@@ -159,7 +160,7 @@ hipError_t launch_commit_leaves(const uint8_t* eds, uint32_t k, uint32_t nsq, vo
                                 uint32_t row0, uint32_t row1, bool init_bad, hipStream_t s);
 // host_out (nsq == 1, optional): page-locked host memory that receives out_bytes (a multiple of
 // 16) starting at row_roots from the DAH launch itself; row_roots, col_roots, dah and status
-// must then be one contiguous block in that order.
+// must then be the parts of one ext::ResultBlock(k, 1) (extend_plan.hpp).
 hipError_t launch_commit_trees(uint32_t k, uint32_t nsq, uint8_t* row_roots, uint8_t* col_roots, uint8_t* dah,
                                int32_t* status, void* work, hipStream_t s, uint8_t* host_out = nullptr,
                                uint32_t out_bytes = 0);
@@ -286,23 +287,55 @@ hipError_t launch_rs_decode_in_square(uint8_t* eds, uint8_t* mask, uint32_t W, c
 
 }  // namespace cel
 
+// Page-locked staging that an enqueued upload may still be reading. An asynchronous entry
+// returns while the copy out of `buf` may still be queued, so the buffer is refilled only after
+// `ev` (recorded behind that copy, `pending` since) has passed: stage_acquire and stage_uploaded
+// (api_common.hpp) are that rule, and but for the ctx's teardown nothing else touches the four
+// fields. A caller may build its table before it asks for the buffer, as commit_enqueue does:
+// nothing in between touches the buffer, so the wait may come after the planning.
+namespace cel {
+struct StagedUpload {
+  void* buf = nullptr;
+  size_t size = 0;
+  hipEvent_t ev = nullptr;
+  bool pending = false;
+};
+}  // namespace cel
+
 // The opaque context of the C ABI.
 struct cel_ctx {
-  static constexpr int kPipe = 4;     // internal streams of the chunked batch pipeline
-  static constexpr int kChunks = 16;  // max chunks per batch call
+  static constexpr int kPipe = cel::ext::kPipeStreams;  // internal streams of the chunked batch pipeline
   int device = 0;
+  // The streams, in the order they are created: with four hardware queues per process a
+  // stream's queue depends on how many were created before it, so the set stays as measured
+  // (dl[2] and dl[3] carry no work: DESIGN.md section 5).
   hipStream_t stream = nullptr;
   hipStream_t sub[kPipe] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_start = nullptr;
+  // EDS downloads (dl[0], beside the hashing) and the k = 512 upload chunks (dl[1])
+  hipStream_t dl[kPipe] = {nullptr, nullptr, nullptr, nullptr};
+  // Events, each named for what it signals. A call records an event before it enqueues a wait
+  // for it, and calls on a ctx hold its lock, so an event serves every path that means the
+  // same thing by it.
+  hipEvent_t ev_start = nullptr;  // the caller's stream at the start of a call: the internal streams begin here
   // CEL_FLAG_CALLER_STREAM batches: the previous one's extension-done event (recorded
   // once ext_pending); the next such batch starts after it (api.cpp)
   hipEvent_t ev_ext = nullptr;
   bool ext_pending = false;
-  hipEvent_t ev_done[kChunks] = {};
-  hipEvent_t ev_rs[kChunks] = {};
-  // EDS downloads of the host pipeline, one per pipeline stream (beside the hashing)
-  hipStream_t dl[kPipe] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_dl[kPipe] = {};
+  // the batch pipelines, by chunk number (ext::HostPlan, ext::PipePlan): chunk c's extension
+  // is done (its EDS may go back), chunk c is committed (the call's stream may go on)
+  hipEvent_t ev_extended[cel::ext::kHostChunks] = {};
+  hipEvent_t ev_committed[cel::ext::kHostChunks] = {};
+  static_assert(cel::ext::kPipeChunks <= cel::ext::kHostChunks, "ev_committed is indexed by either pipeline's chunk");
+  // the one-square path: upload chunk c has arrived, the rows of chunk c are extended (chunk 0
+  // where the square goes up whole), the column pass is done (the block path: the extension)
+  hipEvent_t ev_up[cel::ext::kUp] = {};
+  hipEvent_t ev_rows[cel::ext::kUp] = {};
+  hipEvent_t ev_cols = nullptr;
+  hipEvent_t ev_dl = nullptr;  // the download stream is done with the call's EDS
+  // The repair's two streams (api_repair.cpp, RepairBufs). Its own events: the repair and the
+  // extension never overlap on a ctx, since the ctx lock is held to a call's final sync, so
+  // keeping them apart from the extension's events changes no ordering.
+  hipEvent_t ev_repair_main = nullptr, ev_repair_side[2] = {}, ev_repair_done = nullptr;
   std::mutex mu;
   cel::DeviceTables tables;
   std::string last_error;
@@ -313,27 +346,16 @@ struct cel_ctx {
   // Grow-only page-locked host staging (the repair's axis lists).
   void* hstage = nullptr;
   size_t hstage_size = 0;
-  // Page-locked tables on their way to the device: the plans of the blob commitment calls
-  // (api_commit.cpp), the proof tables of the NMT verifiers (api_verify.cpp), the request
-  // table of the prover (api_prove.cpp) and the namespaces of a namespace plan
-  // (api_namespace.cpp). The asynchronous entry returns while the upload may still be queued,
-  // so the tables have a buffer of their own and the next call waits for ev_plan (recorded
-  // after the upload) before refilling it. plan_stage and plan_uploaded (api_common.hpp) are
-  // that rule, and but for the ctx's teardown nothing else touches these four fields. A caller
-  // may build its table before it asks for the buffer, as commit_enqueue does: nothing in
-  // between touches the buffer, so the wait may come after the planning.
-  void* plan_stage = nullptr;
-  size_t plan_stage_size = 0;
-  hipEvent_t ev_plan = nullptr;
-  bool plan_pending = false;
-  // The square build's plan (api_block.cpp): page-locked staging under the same rule (the
-  // next call waits for ev_sq_up, recorded after the upload, before refilling it), and the
-  // device copy in scratch slot S_SQ, which k_square_build reads until ev_sq_done: the next
-  // call's stream waits for that event before its upload overwrites the plan.
-  void* sq_stage = nullptr;
-  size_t sq_stage_size = 0;
-  hipEvent_t ev_sq_up = nullptr, ev_sq_done = nullptr;
-  bool sq_pending = false;
+  // The two staged uploads of a ctx. plan_up: the plans of the blob commitment calls
+  // (api_commit.cpp), the proof tables of the NMT verifiers (api_verify.cpp), the request table
+  // of the prover (api_prove.cpp) and the namespaces of a namespace plan (api_namespace.cpp),
+  // through plan_stage / plan_uploaded. square_up: the square build's plan (api_block.cpp). Its
+  // device copy, in scratch slot S_SQ, is a second matter: k_square_build reads it until
+  // ev_sq_done, and the next call's stream waits for that event before its upload overwrites
+  // the plan (enqueue_square); sq_built: a build has been enqueued.
+  cel::StagedUpload plan_up, square_up;
+  hipEvent_t ev_sq_done = nullptr;
+  bool sq_built = false;
   // Schedule fuzzing of the repair's two streams (cel_debug_schedule_fuzz; tests only):
   // before each enqueue point, an idle kernel of 0..fuzz_max_us microseconds.
   uint64_t fuzz_state = 0;
