@@ -89,6 +89,156 @@ def mirror_flat(row_trees, cells, namespaces):
                 nodes=np.frombuffer(b"".join(nodes), np.uint8).reshape(-1, 90))
 
 
+# --------------------------------------------------- namespaces that differ at every byte
+LADDER_VALUES = (0x01, 0x02, 0x7E, 0x7F, 0x80, 0x81, 0xFC, 0xFD)  # both sides of 0x80
+SHORT_RUNS = (1, 1, 1, 2, 2, 3)
+SIGN_BYTES = frozenset(range(0, NS, 4)) | {NS - 1}  # the top byte of each compare word
+ABOVE_LADDER = b"\xfd" + b"\xff" * (NS - 1)         # above every ladder value, below N_0
+
+
+def near_parity(b):
+    """N_b: the parity namespace with byte b lowered to 0xFE. N_28 is the tail-padding namespace."""
+    return b"\xff" * b + b"\xfe" + b"\xff" * (NS - 1 - b)
+
+
+def byte_ladder(k, seed, longest=3, row_ends=None, tail=None):
+    """(namespaces, transitions): the k * k namespaces of an ODS, row-major and sorted, in runs of
+    1 .. longest, none the parity namespace; and for every two consecutive distinct namespaces
+    x < y the tuple (pos, b, x, y): pos the flat index of the first share of y, b the first byte
+    at which x and y differ.
+
+    The ladder starts at 0x7F * 29. A transition at byte b bumps x[b] (by 2 at the last byte, so
+    that a namespace lies between x and y) and redraws every later byte from LADDER_VALUES; that
+    always ascends. What chance would leave open is chosen:
+      * b goes round all 29 bytes (stride 7) among the transitions inside a row, and in ascending
+        order among the transitions that fall on a row end, each until every byte has had its turn;
+      * y[b + 1] is drawn below x[b + 1], a later byte that points the other way;
+      * a byte of SIGN_BYTES is redrawn as 0x7F until a bump has taken it across to 0x80.
+    row_ends (default: k >= 32 and runs of at most 3) ends every run at its row's end, so each
+    row end is a transition. tail (default: k == 32) fills the last two rows with N_0 .. N_28,
+    ascending, in runs of 3 (the first six) and 2."""
+    rng = np.random.default_rng(seed)
+    short = longest <= 3
+    row_ends = (short and k >= 32) if row_ends is None else row_ends
+    tail = (k == 32) if tail is None else tail
+    n = k * k - (2 * k if tail else 0)
+    order = [(7 * i) % NS for i in range(NS)]
+    cur = bytearray([0x7F] * NS)
+    need_sign, done, done_row = set(SIGN_BYTES), set(), set()
+    out, trans = [], []
+    while True:
+        r = int(rng.choice(SHORT_RUNS)) if short else int(rng.integers(1, longest + 1))
+        r = min(r, n - len(out))
+        if row_ends:
+            r = min(r, k - len(out) % k)
+        out += [bytes(cur)] * r
+        pos = len(out)
+        if pos == n:
+            break
+        at_end = pos % k == 0
+        had = done_row if at_end else done
+        if len(had) == NS:
+            had.clear()
+        b = next(b for b in (range(NS) if at_end else order) if b not in had)
+        step = 2 if b == NS - 1 else 1
+        while cur[b] + step > 0xFF:  # cannot be bumped: the byte before it
+            b -= 1
+            step = 1
+        assert b >= 0
+        x = bytes(cur)
+        if cur[b] == 0x7F:
+            need_sign.discard(b)
+        cur[b] += step
+        for j in range(b + 1, NS):
+            cur[j] = 0x7F if j in need_sign else int(rng.choice(LADDER_VALUES))
+        contrary = b == NS - 1
+        if b + 1 < NS and x[b + 1] > 0:
+            lower = [v for v in LADDER_VALUES if v < x[b + 1]] or [0]
+            cur[b + 1] = 0x7F if b + 1 in need_sign and 0x7F in lower else int(rng.choice(lower))
+            contrary = True
+        if contrary:
+            had.add(b)
+        trans.append((pos, b, x, bytes(cur)))
+    assert out[-1] < ABOVE_LADDER
+    if tail:
+        for b in range(NS):
+            trans.append((len(out), 0 if b == 0 else b - 1, out[-1], near_parity(b)))
+            out += [near_parity(b)] * (3 if b < 6 else 2)
+    assert len(out) == k * k and PARITY not in out
+    return out, trans
+
+
+def absentees(x, y, b):
+    """The namespaces strictly between the neighbours x < y (first differing at byte b) that sit
+    at the tails' extremes: x[:b + 1] || 0xFF.. just above x's prefix and y[:b + 1] || 0x00.. just
+    below y's. Each differs from one neighbour in late bytes only and from the other at byte b
+    with every later byte pointing the wrong way. One that equals x or y is dropped, both if
+    either is the parity namespace. At the last byte there is no tail: the value between."""
+    if b == NS - 1:
+        return [x[:b] + bytes([x[b] + 1])] if x[b] + 1 < y[b] else []
+    hi, lo = x[:b + 1] + b"\xff" * (NS - 1 - b), y[:b + 1] + bytes(NS - 1 - b)
+    if PARITY in (hi, lo):
+        return []
+    out = [q for q in (hi, lo) if q not in (x, y)]
+    assert all(x < q < y for q in out)
+    return out
+
+
+def ladder_queries(namespaces, trans):
+    """(queries, notes) for a ladder: every present namespace, the absentees of every transition,
+    one namespace below the ladder and ABOVE_LADDER. notes[i] = (what, bytes, pos): "present" with
+    the bytes at which the namespace is decided against its two neighbours, "absent" with the
+    transition's byte and pos, "outside"."""
+    sides = {}
+    for pos, b, x, y in trans:
+        sides.setdefault(x, set()).add(b)
+        sides.setdefault(y, set()).add(b)
+    queries, notes = [], []
+    for p in sorted(set(namespaces)):
+        queries.append(p)
+        notes.append(("present", sides.get(p, set()), None))
+    for pos, b, x, y in trans:
+        for q in absentees(x, y, b):
+            queries.append(q)
+            notes.append(("absent", {b}, pos))
+    queries += [BELOW_ALL, ABOVE_LADDER]
+    notes += [("outside", set(), None)] * 2
+    assert len(set(queries)) == len(queries) and BELOW_ALL < namespaces[0]
+    return queries, notes
+
+
+def ladder_square(k, seed, **kw):
+    """(cells, namespaces, transitions): a 2k x 2k square whose Q0 carries byte_ladder(k, seed)
+    in its shares' first 29 bytes; every other byte of the square is random (no codeword)."""
+    nss, trans = byte_ladder(k, seed, **kw)
+    cells = np.random.default_rng([seed, k]).integers(0, 256, (2 * k, 2 * k, SHARE), dtype=np.uint8)
+    cells[:k, :k, :NS] = np.frombuffer(b"".join(nss), np.uint8).reshape(k, k, NS)
+    return cells, nss, trans
+
+
+def square_row_tree(cells, r):
+    """nmt_ref.Tree of row r of any square by the wrapper's rule: a leaf's namespace is its
+    share's first 29 bytes inside Q0 and the parity namespace elsewhere. hashlib alone."""
+    import nmt_ref
+    w = cells.shape[0]
+    nss = [cells[r, c, :NS].tobytes() if r < w // 2 and c < w // 2 else PARITY for c in range(w)]
+    return nmt_ref.Tree.from_shares(nss, [cells[r, c].tobytes() for c in range(w)])
+
+
+def square_row_tables(cells):
+    """tree_table of every row of the square, as mirror_flat takes them."""
+    return [tree_table(square_row_tree(cells, r).leaves) for r in range(cells.shape[0])]
+
+
+def pair_rule(row, q, w):
+    """What row (its k sorted ODS namespaces; the other w - k leaves are parity) yields for the
+    namespace q, by counting with bytes comparisons: None, or (start, end, kind)."""
+    if not row[0] <= q <= row[-1]:
+        return None  # the root's range, parity ignored
+    lt, le = sum(x < q for x in row), sum(x <= q for x in row)
+    return (lt, le, 0) if le > lt else (lt, lt + 1, 1)
+
+
 # ----------------------------------------------------------------- single rows, proof cases
 def small_ns(v):
     return bytes(27) + bytes([v >> 8 & 0xFF, v & 0xFF])
