@@ -4,8 +4,10 @@ Python view of libcelestia_eds.so (HIP kernels for gfx950 + C ABI), with the
 reference's package names: `da` (pkg/da), `wrapper` (pkg/wrapper), `rsmt2d`
 (github.com/celestiaorg/rsmt2d), plus `device` for the device-resident batch API
 used by bench.py and `block` for the block path from txs (ExtendBlock, ProcessProposal,
-PrepareProposal over cel_block_extend).
+PrepareProposal over cel_block_extend) and `blob` for blobs by namespace out of a square
+(celestia-node's blob service: GetAll, Get, Included, GetProof).
 """
-from . import _lib, block, da, rsmt2d, wrapper  # noqa: F401
+from . import _lib, blob, block, da, rsmt2d, wrapper  # noqa: F401
+from .blob import Blob, parse_sparse_shares  # noqa: F401
 from ._lib import CelError, Context, default_context, load  # noqa: F401
 from .block import ExtendBlock, PrepareProposal, ProcessProposal  # noqa: F401

@@ -820,6 +820,53 @@ class TreeIndex:
             out[int(f["ns_idx"][e])].append((int(f["rows"][e]), p, shares))
         return out
 
+    def blobs_flat(self, ranges, commitments=True, threshold=64):
+        """cel_dev_blobs_plan + cel_dev_blobs_emit over `ranges` ((start, end) in row-major ODS
+        index) of the resident square: (records, range status, data, commitments [n][32] or
+        None) as host arrays; blob i's bytes are data[rec.data_off : rec.data_off + rec.len]."""
+        from . import blob as _blob
+        torch, c = self._torch, self.ctx
+        n = len(ranges)
+        starts = np.array([r[0] for r in ranges] or [0], np.uint32)
+        ends = np.array([r[1] for r in ranges] or [0], np.uint32)
+        if any(not (0 <= int(a) <= int(b) <= self.k * self.k) for a, b in ranges):
+            raise CelError(_lib.EINVAL, f"a range is outside the {self.k}x{self.k} square or has start > end")
+        total = int(sum(int(b) - int(a) for a, b in ranges))
+        status = np.zeros(max(n, 1), np.uint32)
+        cnt, tb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        with torch.cuda.stream(self._stream):
+            d_work = torch.empty((max(c.lib.cel_dev_blobs_workspace_size(total, n), 16),), dtype=torch.uint8,
+                                 device=self._dev)
+            cap = max(total, 1)  # a blob has at least one share
+            recs = (_blob.BlobRec * cap)()
+            c.check(c.lib.cel_dev_blobs_plan(c.handle, self._ptr(self.d_eds), self.k, n, _p(starts), _p(ends), cap,
+                                             recs, _p(status), ctypes.byref(cnt), ctypes.byref(tb), self._ptr(d_work),
+                                             self._stream_ptr()))
+            m, nbytes = cnt.value, tb.value
+            recs = list(recs[:m])
+            d_data = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=self._dev)
+            d_com = d_cwork = None
+            if commitments and m:
+                d_com = torch.empty((m, 32), dtype=torch.uint8, device=self._dev)
+                size = c.lib.cel_dev_commitments_workspace_size(sum(r.shares for r in recs), m)
+                d_cwork = torch.empty((size,), dtype=torch.uint8, device=self._dev)
+            c.check(c.lib.cel_dev_blobs_emit(c.handle, self._ptr(self.d_eds), self.k, m, self._ptr(d_data),
+                                             self._ptr(d_com) if d_com is not None else None, threshold,
+                                             self._ptr(d_work), self._ptr(d_cwork) if d_cwork is not None else None,
+                                             self._stream_ptr()))
+            self._stream.synchronize()
+            data = d_data[:nbytes].cpu().numpy()
+            com = d_com.cpu().numpy() if d_com is not None else (np.zeros((0, 32), np.uint8) if commitments else None)
+        return recs, status[:n], data, com
+
+    def blobs(self, ranges, commitments=True, threshold=64):
+        """go-square parseSparseShares over each range of ODS shares of the resident square, on
+        the device: per range a list of blob.Blob (with commitments=True each with its share
+        commitment), or the blob.BlobParseError of a range that does not parse."""
+        from . import blob as _blob
+        recs, status, data, com = self.blobs_flat(ranges, commitments=commitments, threshold=threshold)
+        return _blob.blobs_from_records(recs, status, data, com, len(ranges))
+
 
 def NewShareInclusionProofsBatch(eds, requests, ctx=None):
     """NewShareInclusionProofFromEDS(eds, namespace, start, end) for every (namespace, start,

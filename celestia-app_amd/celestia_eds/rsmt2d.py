@@ -211,6 +211,52 @@ class ExtendedDataSquare:
                         [leaves[j].tobytes() for j in range(int(leaf_off[e]), int(leaf_off[e + 1]))]))
         return out
 
+    def Blobs(self, namespaces, commitments=True, threshold=64):
+        """The blobs of `namespaces` (29 bytes each, no reserved ones) in this square, what
+        celestia-node's blob.GetAll serves: per namespace a list of blob.Blob (each with its share
+        commitment and the ODS index of its first share), or the blob.BlobParseError of a
+        namespace whose shares do not parse. The host-memory form: cel_namespace_rows finds the
+        shares, cel_namespace_ods_ranges turns them into ODS ranges, cel_blobs_by_range uploads,
+        parses, gathers and commits."""
+        from . import blob as _blob
+        nss = _blob.check_blob_namespaces(namespaces)
+        n = len(nss)
+        if n == 0:
+            return []
+        c, k = self.ctx, self.Width() // 2
+        cells = np.ascontiguousarray(self.cells, dtype=np.uint8)
+        nsa = np.frombuffer(b"".join(nss), np.uint8).copy()
+        cnt, tl, tn = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        c.check(c.lib.cel_namespace_rows(c.handle, _p(cells), k, n, _p(nsa), 0, 0, 0, *([None] * 9),
+                                         ctypes.byref(cnt), ctypes.byref(tl), ctypes.byref(tn)))
+        m = cnt.value
+        plan = dict(ns_idx=np.zeros(m, np.uint32), rows=np.zeros(m, np.uint32), starts=np.zeros(m, np.int32),
+                    ends=np.zeros(m, np.int32), kinds=np.zeros(m, np.uint8))
+        if m:
+            leaf_off, node_off = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64)
+            leaves = np.zeros((max(tl.value, 1), _lib.SHARE_SIZE), np.uint8)
+            nodes = np.zeros((max(tn.value, 1), _lib.NMT_NODE_SIZE), np.uint8)
+            c.check(c.lib.cel_namespace_rows(c.handle, _p(cells), k, n, _p(nsa), m, tl.value, tn.value,
+                                             _p(plan["ns_idx"]), _p(plan["rows"]), _p(plan["starts"]), _p(plan["ends"]),
+                                             _p(plan["kinds"]), _p(leaf_off), _p(node_off), _p(leaves), _p(nodes),
+                                             ctypes.byref(cnt), ctypes.byref(tl), ctypes.byref(tn)))
+        ranges = _blob.ods_ranges(k, n, plan)
+        starts = np.array([a for a, _ in ranges], np.uint32)
+        ends = np.array([b for _, b in ranges], np.uint32)
+        status = np.zeros(n, np.uint32)
+        nb, tb = ctypes.c_uint64(), ctypes.c_uint64()
+        c.check(c.lib.cel_blobs_by_range(c.handle, _p(cells), k, n, _p(starts), _p(ends), 0, 0, None, _p(status), None,
+                                         None, threshold, ctypes.byref(nb), ctypes.byref(tb)))
+        cap, nbytes = nb.value, tb.value
+        recs = (_blob.BlobRec * max(cap, 1))()
+        data = np.zeros(max(nbytes, 1), np.uint8)
+        com = np.zeros((max(cap, 1), 32), np.uint8) if commitments else None
+        if cap:
+            c.check(c.lib.cel_blobs_by_range(c.handle, _p(cells), k, n, _p(starts), _p(ends), cap, nbytes, recs,
+                                             _p(status), _p(data), _p(com) if commitments else None, threshold,
+                                             ctypes.byref(nb), ctypes.byref(tb)))
+        return _blob.blobs_from_records(list(recs[:cap]), status, data, com, n)
+
     def SampleProofs(self, coords):
         """Samples of this square with their single-leaf NMT proofs, in one device batch
         (cel_prove_samples: upload, tree index, proofs, download). coords: (row, col, axis)

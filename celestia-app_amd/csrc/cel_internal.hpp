@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/celestia_eds.h"
 #include "extend_plan.hpp"
@@ -360,6 +361,15 @@ struct cel_ctx {
   // before each enqueue point, an idle kernel of 0..fuzz_max_us microseconds.
   uint64_t fuzz_state = 0;
   uint32_t fuzz_max_us = 0;
+  // The last blob plan made on this ctx (api_blobs.cpp): the workspace that holds it, what it
+  // was made for, and its records as the plan call downloaded them. The emit call builds the
+  // commitments' plan from them without waiting for the device.
+  struct BlobPlan {
+    const void* d_work = nullptr;
+    uint32_t k = 0, n_ranges = 0;
+    uint64_t total = 0, total_bytes = 0;
+    std::vector<cel_blob_rec> recs;
+  } blob_plan;
   // cel_extend_sharded's plan (buffers, streams, RCCL communicators), kept while the device
   // list, k and flags stay the same (api_multi.cpp)
   cel_shard_plan* shard_cache = nullptr;

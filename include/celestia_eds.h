@@ -574,6 +574,75 @@ cel_status cel_dev_nmt_verify_namespace_batch(cel_ctx* ctx, uint32_t n, const in
                                               uint32_t nroots, const uint32_t* root_idx, void* d_ok,
                                               void* d_work, void* stream);
 
+/* ------------------------------------------------- blobs by range
+ * go-square v1.1.0 parseSparseShares over runs of ODS shares of a resident square, and the
+ * blobs' share commitments: what celestia-node's blob service (GetAll, Get, Included) builds
+ * from the shares of a namespace. A range is [start, end) in row-major ODS index (share s is
+ * cell (s / k, s % k) of Q0); ranges may overlap or repeat. The shares of a range in order: a
+ * share version other than 0 fails the range (CEL_BLOB_EVERSION); tail padding, primary
+ * reserved padding and namespace padding (a sequence start of length 0) are skipped; any other
+ * sequence start opens a blob (namespace bytes 0 .. 28, length bytes 30 .. 33 big-endian,
+ * payload bytes 34 .. 511); a continuation appends its bytes 30 .. 511 to the blob opened last
+ * in the range, whatever its own namespace, and fails the range with none open
+ * (CEL_BLOB_ENOSTART). A blob closes at the next start or the range's end; fewer bytes than
+ * its length fail the range (CEL_BLOB_ESHORT), more are trimmed. A failed range has its first
+ * error as status and yields no blobs; the other ranges are unaffected.
+ *
+ * cel_dev_blobs_plan: the blobs of n_ranges ranges (host arrays starts, ends) of the square at
+ * d_eds (2k*2k*512, 16-byte aligned; only Q0 is read), in (range, position) order, into recs
+ * (cap records) and range_status (n_ranges words, nullable); *n_blobs and *total_bytes, the
+ * size of the data buffer: blob b's bytes go to data_off, a multiple of 16, and take len rounded
+ * up to 16. recs[].shares is the number of shares the blob was found with. Synchronous on
+ * stream: the count depends on the data. cap = 0 with recs NULL: count only. cap below the
+ * count: CEL_EINVAL, both numbers in cel_last_error, the counts and range_status set. The plan
+ * stays in d_work (cel_dev_blobs_workspace_size(total shares of the ranges, n_ranges) bytes,
+ * 16-byte aligned) for cel_dev_blobs_emit, which must be the next blob call on this ctx with
+ * that workspace. CEL_EINVAL: nil argument, misalignment, a k that is not a power of two up to
+ * 512, start > end, end > k*k, 2^31 shares or more in all. n_ranges = 0 is CEL_OK.
+ * cel_dev_blobs_emit: the bytes of the first n_blobs blobs of the plan in d_work (no more than
+ * it holds) into d_data (16-byte aligned, total_bytes bytes; the bytes between a blob's end and
+ * the next multiple of 16 are zero) and, with d_commitments not NULL, their share commitments
+ * (32 bytes each, inclusion.CreateCommitment) from there: d_commit_work is
+ * cel_dev_commitments_workspace_size(sum of recs[].shares, n_blobs) bytes. Asynchronous on
+ * stream.
+ * cel_blobs_by_range: the same for a square in host memory: upload, plan, emit, download.
+ * The counts and range_status always come back; recs, data_out and commitments_out
+ * (nullable) are written when cap and data_cap (bytes) suffice, else CEL_EINVAL; both 0 with
+ * recs and data_out NULL: count only.
+ * cel_namespace_ods_ranges (host only): the inclusion entries of a namespace plan
+ * (cel_dev_namespace_plan's arrays) as one ODS range per queried namespace, from the first
+ * entry's (row, start) to the last entry's (row, end); a namespace without one gets the empty
+ * range [0, 0). CEL_EINVAL: an entry outside Q0 (row or end beyond k), an ns_idx beyond
+ * n_namespaces, or entries of a namespace that are not one contiguous run of ODS shares (an
+ * unordered square). */
+#define CEL_BLOB_EVERSION 1 /* range status codes; 0 = ok */
+#define CEL_BLOB_ENOSTART 2
+#define CEL_BLOB_ESHORT 3
+typedef struct cel_blob_rec { /* 64 bytes */
+  uint32_t range, start, shares, share_version;
+  uint32_t len, reserved;
+  uint64_t data_off;
+  uint8_t ns[32]; /* 29 bytes, then zeros */
+} cel_blob_rec;
+size_t cel_dev_blobs_workspace_size(uint64_t total_shares, uint32_t n_ranges);
+cel_status cel_dev_blobs_plan(cel_ctx* ctx, const void* d_eds, uint32_t k, uint32_t n_ranges,
+                              const uint32_t* starts, const uint32_t* ends, uint64_t cap,
+                              cel_blob_rec* recs, uint32_t* range_status, uint64_t* n_blobs,
+                              uint64_t* total_bytes, void* d_work, void* stream);
+cel_status cel_dev_blobs_emit(cel_ctx* ctx, const void* d_eds, uint32_t k, uint64_t n_blobs,
+                              void* d_data, void* d_commitments, uint32_t subtree_root_threshold,
+                              void* d_work, void* d_commit_work, void* stream);
+cel_status cel_blobs_by_range(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32_t n_ranges,
+                              const uint32_t* starts, const uint32_t* ends, uint64_t cap,
+                              uint64_t data_cap, cel_blob_rec* recs, uint32_t* range_status,
+                              uint8_t* data_out, uint8_t* commitments_out,
+                              uint32_t subtree_root_threshold, uint64_t* n_blobs,
+                              uint64_t* total_bytes);
+cel_status cel_namespace_ods_ranges(uint32_t k, uint32_t n_namespaces, uint64_t n_entries,
+                                    const uint32_t* ns_idx, const uint32_t* rows,
+                                    const int32_t* starts, const int32_t* ends, const uint8_t* kinds,
+                                    uint32_t* range_start, uint32_t* range_end);
+
 /* Blob share commitments from an EDS (pkg/inclusion).
  * cel_commitment_paths: calculateCommitmentPaths (paths.go:16-47) for a blob of
  * blob_share_len shares placed at the first aligned index >= start of a square of
