@@ -18,6 +18,8 @@ OK, EINVAL, ENOTPOW2, ECHUNK, ETOOBIG, EORDER, ETOOFEW, EBYZANTINE, EUNREPAIRABL
 FLAG_ORDER_CHECK = 0x1
 NS_INCLUSION, NS_ABSENCE = 0, 1
 BLOB_EVERSION, BLOB_ENOSTART, BLOB_ESHORT = 1, 2, 3  # range status codes of the blob parser
+TX_EVERSION, TX_ENAMESPACE, TX_ERESERVED, TX_EVARINT = 1, 2, 3, 4  # of the compact share parser
+TX_FHINTS = 1  # range flag: the reserved bytes disagree with the sequential parse
 FLAG_PARITY_ONLY = 0x2
 FLAG_CALLER_STREAM = 0x4
 FLAG_SHARD_EXCHANGE = 0x8
@@ -52,6 +54,7 @@ EXPORTS = [
     "cel_dev_nmt_verify_namespace_batch",
     "cel_dev_blobs_workspace_size", "cel_dev_blobs_plan", "cel_dev_blobs_emit", "cel_blobs_by_range",
     "cel_namespace_ods_ranges",
+    "cel_dev_txs_workspace_size", "cel_dev_txs_plan", "cel_dev_txs_emit", "cel_txs_by_range",
 ]
 
 _lib = None
@@ -167,6 +170,10 @@ def load():
             "cel_dev_blobs_emit": (i32, [P, P, u32, u64, P, P, u32, P, P, P]),
             "cel_blobs_by_range": (i32, [P, P, u32, u32, P, P, u64, u64, P, P, P, P, u32, P, P]),
             "cel_namespace_ods_ranges": (i32, [u32, u32, u64, P, P, P, P, P, P, P]),
+            "cel_dev_txs_workspace_size": (sz, [u64, u32]),
+            "cel_dev_txs_plan": (i32, [P, P, u32, u32, P, P, P, P, P, P, P, P]),
+            "cel_dev_txs_emit": (i32, [P, P, u32, u64, P, P, P, P, P]),
+            "cel_txs_by_range": (i32, [P, P, u32, u32, P, P, u64, u64, P, P, P, P, P, P, P]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(l, name)

@@ -867,6 +867,48 @@ class TreeIndex:
         recs, status, data, com = self.blobs_flat(ranges, commitments=commitments, threshold=threshold)
         return _blob.blobs_from_records(recs, status, data, com, len(ranges))
 
+    def txs_flat(self, ranges, hashes=True):
+        """cel_dev_txs_plan + cel_dev_txs_emit over `ranges` ((start, end) in row-major ODS index)
+        of the resident square: (records, range status, range flags, data, hashes [n][32] or
+        None) as host arrays; unit i's bytes are data[rec.data_off : rec.data_off + rec.len]."""
+        from . import square as _square
+        torch, c = self._torch, self.ctx
+        n = len(ranges)
+        starts = np.array([r[0] for r in ranges] or [0], np.uint32)
+        ends = np.array([r[1] for r in ranges] or [0], np.uint32)
+        if any(not (0 <= int(a) <= int(b) <= self.k * self.k) for a, b in ranges):
+            raise CelError(_lib.EINVAL, f"a range is outside the {self.k}x{self.k} square or has start > end")
+        total = int(sum(int(b) - int(a) for a, b in ranges))
+        status, flags = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        cnt, tb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        with torch.cuda.stream(self._stream):
+            d_work = torch.empty((max(c.lib.cel_dev_txs_workspace_size(total, n), 16),), dtype=torch.uint8,
+                                 device=self._dev)
+            c.check(c.lib.cel_dev_txs_plan(c.handle, self._ptr(self.d_eds), self.k, n, _p(starts), _p(ends), _p(status),
+                                           _p(flags), ctypes.byref(cnt), ctypes.byref(tb), self._ptr(d_work),
+                                           self._stream_ptr()))
+            m, nbytes = cnt.value, tb.value
+            d_recs = torch.empty((max(m, 1) * ctypes.sizeof(_square.TxRec),), dtype=torch.uint8, device=self._dev)
+            d_data = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=self._dev)
+            d_hash = torch.empty((max(m, 1), 32), dtype=torch.uint8, device=self._dev) if hashes else None
+            c.check(c.lib.cel_dev_txs_emit(c.handle, self._ptr(self.d_eds), self.k, m, self._ptr(d_recs),
+                                           self._ptr(d_data), self._ptr(d_hash) if hashes else None,
+                                           self._ptr(d_work), self._stream_ptr()))
+            self._stream.synchronize()
+            raw = d_recs.cpu().numpy().tobytes()
+            recs = list((_square.TxRec * m).from_buffer_copy(raw[:m * ctypes.sizeof(_square.TxRec)]))
+            data = d_data[:nbytes].cpu().numpy()
+            hs = d_hash[:m].cpu().numpy() if hashes else None
+        return recs, status[:n], flags[:n], data, hs
+
+    def txs(self, ranges):
+        """The compact share parser over each range of ODS shares of the resident square, on the
+        device: per range the list of its units (txs, or PayForBlob index wrappers), or the
+        square.TxParseError of a range that does not parse."""
+        from . import square as _square
+        recs, status, _, data, _ = self.txs_flat(ranges, hashes=False)
+        return _square.units_from_records(recs, status, data, len(ranges))
+
 
 def NewShareInclusionProofsBatch(eds, requests, ctx=None):
     """NewShareInclusionProofFromEDS(eds, namespace, start, end) for every (namespace, start,

@@ -257,6 +257,39 @@ class ExtendedDataSquare:
                                              ctypes.byref(nb), ctypes.byref(tb)))
         return _blob.blobs_from_records(list(recs[:cap]), status, data, com, n)
 
+    def Txs(self, hashes=False):
+        """The units of this square's two compact namespaces, what shares.ParseTxs and
+        square.Deconstruct read: (txs, PayForBlob index wrappers), or with hashes=True
+        ((txs, their SHA-256), (wrappers, theirs)). The host-memory form: the runs of the two
+        namespaces at the head of the ODS are found here, cel_txs_by_range uploads, parses,
+        gathers and hashes. Shares that do not parse raise square.TxParseError."""
+        from . import square as _square
+        c, k = self.ctx, self.Width() // 2
+        cells = np.ascontiguousarray(self.cells, dtype=np.uint8)
+        ranges = _square._compact_runs(cells[:k, :k].reshape(k * k, _lib.SHARE_SIZE))
+        starts = np.array([a for a, _ in ranges], np.uint32)
+        ends = np.array([b for _, b in ranges], np.uint32)
+        status, flags = np.zeros(2, np.uint32), np.zeros(2, np.uint32)
+        nu, tb = ctypes.c_uint64(), ctypes.c_uint64()
+        c.check(c.lib.cel_txs_by_range(c.handle, _p(cells), k, 2, _p(starts), _p(ends), 0, 0, None, _p(status),
+                                       _p(flags), None, None, ctypes.byref(nu), ctypes.byref(tb)))
+        cap, nbytes = nu.value, tb.value
+        recs = (_square.TxRec * max(cap, 1))()
+        data = np.zeros(max(nbytes, 1), np.uint8)
+        hs = np.zeros((max(cap, 1), 32), np.uint8)
+        if cap:
+            c.check(c.lib.cel_txs_by_range(c.handle, _p(cells), k, 2, _p(starts), _p(ends), cap, nbytes, recs,
+                                           _p(status), _p(flags), _p(data), _p(hs) if hashes else None,
+                                           ctypes.byref(nu), ctypes.byref(tb)))
+        out = _square.units_from_records(list(recs[:cap]), status, data, 2)
+        for got in out:
+            if isinstance(got, Exception):
+                raise got
+        if not hashes:
+            return tuple(out)
+        n_tx = len(out[0])
+        return (out[0], [h.tobytes() for h in hs[:n_tx]]), (out[1], [h.tobytes() for h in hs[n_tx:cap]])
+
     def SampleProofs(self, coords):
         """Samples of this square with their single-leaf NMT proofs, in one device batch
         (cel_prove_samples: upload, tree index, proofs, download). coords: (row, col, axis)

@@ -370,6 +370,13 @@ struct cel_ctx {
     uint64_t total = 0, total_bytes = 0;
     std::vector<cel_blob_rec> recs;
   } blob_plan;
+  // The last tx plan made on this ctx (api_txs.cpp): the workspace that holds it, what it was
+  // made for and its counts. Its records stay on the device.
+  struct TxPlan {
+    const void* d_work = nullptr;
+    uint32_t k = 0, n_ranges = 0;
+    uint64_t total = 0, n_units = 0, total_bytes = 0;
+  } tx_plan;
   // cel_extend_sharded's plan (buffers, streams, RCCL communicators), kept while the device
   // list, k and flags stay the same (api_multi.cpp)
   cel_shard_plan* shard_cache = nullptr;

@@ -643,6 +643,76 @@ cel_status cel_namespace_ods_ranges(uint32_t k, uint32_t n_namespaces, uint64_t 
                                     const int32_t* starts, const int32_t* ends, const uint8_t* kinds,
                                     uint32_t* range_start, uint32_t* range_end);
 
+/* ------------------------------------------------- txs by range
+ * go-square v1.1.0 parseCompactShares over runs of ODS shares of a resident square: the txs of
+ * the tx namespace (28 zero bytes, 0x01) and the index wrappers of the PayForBlob namespace
+ * (28 zero bytes, 0x04), what shares.ParseTxs and square.Deconstruct read. Ranges are those of
+ * the blob calls; they may repeat, overlap or be empty. A range's status is its first error in
+ * this order, a failed range yields no units, the other ranges are unaffected:
+ *   1. a share whose info byte has a version other than 0: CEL_TX_EVERSION;
+ *   2. a share whose namespace is neither of the two: CEL_TX_ENAMESPACE (narrower than go-square,
+ *      which would read it with another header size); both may be mixed in one range;
+ *   3. the stream: a share's header size h is 38 with the sequence-start bit, else 34; the first
+ *      share's reserved value R, big-endian at bytes h-4 .. h-1, gives CEL_TX_ERESERVED when
+ *      R >= 512, no bytes when R == 0, else the bytes R .. 511 (also where R < h); every later
+ *      share gives its bytes h .. 511 whatever its reserved value. The sequence length is not
+ *      read;
+ *   4. the units, from stream position p = 0: stop at the stream's end; read a uvarint from up to
+ *      10 bytes at p, zeros behind the end (more than 10 bytes, or a 10th byte above 1:
+ *      CEL_TX_EVARINT); with its value L and n the length of L's canonical encoding, L == 0
+ *      stops (padding), L above the bytes left behind p + n stops (a cut unit is dropped without
+ *      error), else the unit is the stream's bytes [p + n, p + n + L) and p += n + L.
+ * range_flags (nullable, n_ranges words): CEL_TX_FHINTS where the reserved bytes of the later
+ * shares disagree with that parse: up to the share in which the last unit begins, a share in
+ * which a unit begins does not name the first such unit's byte, or one in which none begins
+ * holds a usable value (h <= R < 512). The device finds the units share by share from these
+ * values and parses such a range serially instead; the result is the same. An honest builder
+ * never produces it.
+ *
+ * cel_tx_rec: (share, shares) are the ODS index of the share in which the unit's length prefix
+ * begins and the number of shares that prefix and unit touch: cel_square_tx_range's
+ * [start, end) = [share, share + shares), which counts the prefix too. share_off is the byte of
+ * that share at which the prefix begins; len the unit's length; its bytes go to data_off, a
+ * multiple of 16, and take len rounded up to 16.
+ *
+ * cel_dev_txs_plan: counts the units of n_ranges ranges of the square at d_eds (2k*2k*512,
+ * 16-byte aligned; only Q0 is read): *n_units, *total_bytes, range_status and range_flags (both
+ * nullable). Synchronous on stream: the counts depend on the data. The plan stays in d_work
+ * (cel_dev_txs_workspace_size(total shares of the ranges, n_ranges) bytes, 16-byte aligned,
+ * linear in both) for cel_dev_txs_emit, which must be the next tx call on this ctx with that
+ * workspace. CEL_EINVAL as for cel_dev_blobs_plan; n_ranges = 0 is CEL_OK.
+ * cel_dev_txs_emit: the records of the first n_units units of the plan (no more than it holds),
+ * in (range, position) order, into d_recs (device memory, 16-byte aligned), their bytes into
+ * d_data (16-byte aligned, total_bytes bytes; zeros up to the next multiple of 16) and, with
+ * d_hashes not NULL, the SHA-256 of each unit's bytes (32 bytes each): the tx hash of a unit of
+ * the tx namespace, the hash of the index wrapper as stored of a PayForBlob unit. Asynchronous
+ * on stream.
+ * cel_txs_by_range: the same for a square in host memory: upload, plan, emit, download. The
+ * counts, range_status and range_flags always come back; recs, data_out and hashes_out
+ * (nullable) are written when cap and data_cap (bytes) suffice, else CEL_EINVAL; both 0 with
+ * recs and data_out NULL: count only. */
+#define CEL_TX_EVERSION 1 /* range status codes; 0 = ok */
+#define CEL_TX_ENAMESPACE 2
+#define CEL_TX_ERESERVED 3
+#define CEL_TX_EVARINT 4
+#define CEL_TX_FHINTS 1u /* range flag */
+typedef struct cel_tx_rec { /* 32 bytes */
+  uint32_t range, share, share_off, shares;
+  uint64_t len, data_off;
+} cel_tx_rec;
+size_t cel_dev_txs_workspace_size(uint64_t total_shares, uint32_t n_ranges);
+cel_status cel_dev_txs_plan(cel_ctx* ctx, const void* d_eds, uint32_t k, uint32_t n_ranges,
+                            const uint32_t* starts, const uint32_t* ends, uint32_t* range_status,
+                            uint32_t* range_flags, uint64_t* n_units, uint64_t* total_bytes,
+                            void* d_work, void* stream);
+cel_status cel_dev_txs_emit(cel_ctx* ctx, const void* d_eds, uint32_t k, uint64_t n_units,
+                            void* d_recs, void* d_data, void* d_hashes, void* d_work, void* stream);
+cel_status cel_txs_by_range(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint32_t n_ranges,
+                            const uint32_t* starts, const uint32_t* ends, uint64_t cap,
+                            uint64_t data_cap, cel_tx_rec* recs, uint32_t* range_status,
+                            uint32_t* range_flags, uint8_t* data_out, uint8_t* hashes_out,
+                            uint64_t* n_units, uint64_t* total_bytes);
+
 /* Blob share commitments from an EDS (pkg/inclusion).
  * cel_commitment_paths: calculateCommitmentPaths (paths.go:16-47) for a blob of
  * blob_share_len shares placed at the first aligned index >= start of a square of
