@@ -6,6 +6,7 @@ Mirrors the pieces of github.com/celestiaorg/rsmt2d that celestia-app uses
   ComputeExtendedDataSquare, ImportExtendedDataSquare, ExtendedDataSquare.{RowRoots,
   ColRoots, Row, Col, GetCell, Flattened, Width, Repair}
   RepairFromSamples: cells with NMT inclusion proofs, verified on the device, then Repair
+  RepairBatch: Repair over many squares in one device call, one outcome per square
   ExtendedDataSquare.SampleProofs: the producer of such samples, one device batch
 All arithmetic runs in libcelestia_eds.so (HIP); this module marshals bytes.
 
@@ -345,6 +346,61 @@ class ExtendedDataSquare:
         self._row_roots = np.frombuffer(rr.tobytes(), np.uint8).reshape(w, -1).copy()
         self._col_roots = np.frombuffer(cr.tobytes(), np.uint8).reshape(w, -1).copy()
         return mask
+
+
+def RepairBatch(squares, row_roots, col_roots, presents=None, ctx=None):
+    """ExtendedDataSquare.Repair over many squares of one width in one device call
+    (cel_repair_batch): squares[i] an ExtendedDataSquare or a (W, W, 512) array, row_roots[i] /
+    col_roots[i] its 2k roots, presents[i] its mask (None: all present). Returns one item per
+    square: the repaired ExtendedDataSquare (with its _mask), or, not raised, the error Repair
+    would raise for that square alone (ErrByzantineData with Axis, Index and Shares,
+    ErrUnrepairableDataSquare, CelError(EBADROOT)); an error carries `.square`, the
+    most-repaired ExtendedDataSquare with the mask it is valid under, as Repair leaves on self."""
+    ctx = ctx or _lib.default_context()
+    n = len(squares)
+    if n == 0:
+        return []
+    if len(row_roots) != n or len(col_roots) != n or (presents is not None and len(presents) != n):
+        raise CelError(_lib.EINVAL, f"need roots (and masks) for each of the {n} squares")
+    cells = np.stack([np.asarray(s.cells if isinstance(s, ExtendedDataSquare) else s, np.uint8) for s in squares])
+    w = cells.shape[1]
+    if cells.shape != (n, w, w, _lib.SHARE_SIZE):
+        raise CelError(_lib.EINVAL, f"squares must be {w} x {w} cells of {_lib.SHARE_SIZE} bytes")
+    cells = np.ascontiguousarray(cells)
+    mask = (np.ones((n, w, w), np.uint8) if presents is None
+            else np.ascontiguousarray(np.stack([np.asarray(p, np.uint8) for p in presents])))
+    rr = np.frombuffer(b"".join(b"".join(bytes(x) for x in r) for r in row_roots), np.uint8).copy()
+    cr = np.frombuffer(b"".join(b"".join(bytes(x) for x in c) for c in col_roots), np.uint8).copy()
+    if mask.shape != (n, w, w) or rr.size != n * w * _lib.NMT_NODE_SIZE or cr.size != rr.size:
+        raise CelError(_lib.EINVAL, f"need {w} x {w} masks and {w} row and column roots per square")
+    status = np.zeros(n, np.int32)
+    ba, bi = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    bs = np.zeros((n, w, _lib.SHARE_SIZE), np.uint8)
+    bp = np.zeros((n, w), np.uint8)
+    ctx.check(ctx.lib.cel_repair_batch(ctx.handle, _p(cells), _p(mask), n, w // 2, _lib.SHARE_SIZE, _p(rr), _p(cr),
+                                       _p(status), _p(ba), _p(bi), _p(bs), _p(bp)))
+    out = []
+    for i in range(n):
+        sq = ExtendedDataSquare(cells[i], ctx=ctx)
+        sq._mask = mask[i]
+        st = int(status[i])
+        if st == _lib.OK:
+            node = _lib.NMT_NODE_SIZE
+            sq._row_roots = rr[i * w * node:(i + 1) * w * node].reshape(w, node).copy()
+            sq._col_roots = cr[i * w * node:(i + 1) * w * node].reshape(w, node).copy()
+            out.append(sq)
+            continue
+        dirn = "column" if ba[i] else "row"
+        if st == _lib.EBYZANTINE:
+            err = ErrByzantineData(int(ba[i]), int(bi[i]), f"byzantine {dirn} {int(bi[i])}",
+                                   [bs[i, j].tobytes() if bp[i, j] else None for j in range(w)])
+        elif st == _lib.EUNREPAIRABLE:
+            err = ErrUnrepairableDataSquare()
+        else:
+            err = CelError(st, f"bad root input: {'col' if ba[i] else 'row'} {int(bi[i])}")
+        err.square = sq
+        out.append(err)
+    return out
 
 
 def _check_codec(codec):

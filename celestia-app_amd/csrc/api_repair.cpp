@@ -1,5 +1,5 @@
-// C ABI of the repair (include/celestia_eds.h): cel_repair, cel_dev_repair and their test
-// hooks, split from api.cpp. Device control of rsmt2d's Repair over a device-resident
+// C ABI of the repair (include/celestia_eds.h): cel_repair, cel_dev_repair, their batch forms
+// (cel_dev_repair_batch, cel_repair_batch) and their test hooks, split from api.cpp. Device control of rsmt2d's Repair over a device-resident
 // EDS: the buffers, the two streams and what is enqueued on them. What to solve and check,
 // and in which order, is the host planner's (repair_plan.hpp); every decode, re-encode,
 // compare and root runs in the HIP kernels.
@@ -661,6 +661,332 @@ static cel_status repair_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds, uint8
   return st;
 }
 
+// ------------------------------------------------------------ batch of squares
+//
+// cel_dev_repair_batch: the schedule of repair_core over n squares of one k (32, 64, 128: the
+// in-square kernels) at once. Every pass is the merged pass of repair_plan.hpp (BatchPasses):
+// one decode launch on the main stream and one check launch on the side stream serve every
+// square that has axes in it, one commit takes all n squares' roots, and one copy brings the
+// roots and flags back. Only the verdict is per square.
+//
+// Every scratch slot and the page-locked stage start with the single-square layout (the same
+// walk as RepairBufs), the batch's regions after it: a square whose SOLVE or ORTH check
+// fails is replayed alone by repair_exact through a RepairBufs whose eds is that square's
+// slice of the batch, without a reallocation under the batch's buffers.
+struct BatchBufs {
+  uint32_t W, n;
+  RepairBufs one;     // the single-square prefix of every slot (eds unset)
+  uint8_t* eds;       // [n][W][W][512]
+  uint8_t* mask;      // [n][W*W], then the first pass's entries (one upload for both)
+  int32_t* list0;     // [n*W]
+  uint8_t* work;      // the n-square commit's workspace
+  uint8_t* roots;     // [n][W][90] row roots, [n][W][90] column roots, then the flags
+  int32_t* flags;     // [n][2][W] by (square, direction, axis)
+  uint8_t* hroots;    // page-locked copy of roots + flags (one D2H of res_bytes)
+  int32_t* hflags;
+  size_t res_bytes;
+  int32_t* idx;       // [kIdxSlots][n*W] device entry lists
+  int32_t* hidx;      // page-locked staging of the same
+  uint8_t* hmask;     // page-locked staging of masks + first entries
+  int32_t* hlist0;
+  uint32_t slot;
+  hipStream_t main, side;
+  hipEvent_t ev_main, ev_done;
+  size_t slot_len() const { return (size_t)n * W; }
+};
+
+static void take_batch_mask_list(Carver& c, const BatchBufs& b, uint8_t** mask, int32_t** list0) {
+  *mask = c.take<uint8_t>((size_t)b.n * b.W * b.W);
+  *list0 = c.take<int32_t>(b.slot_len() * 4);
+}
+static void take_batch_results(Carver& c, const BatchBufs& b, uint8_t** roots, int32_t** flags) {
+  *roots = c.take<uint8_t>((size_t)b.n * 2 * b.W * kNode);
+  *flags = c.take<int32_t>((size_t)b.n * 2 * b.W * 4);
+}
+static void carve_batch_in(Carver& c, BatchBufs& b) { carve_in(c, b.one); }  // S_IN: the replay's alone
+static void carve_batch_aux(Carver& c, BatchBufs& b) {                       // S_AUX
+  carve_aux(c, b.one);
+  b.idx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
+}
+static void carve_batch_mask(Carver& c, BatchBufs& b) {  // S_MASK
+  carve_mask(c, b.one);
+  take_batch_mask_list(c, b, &b.mask, &b.list0);
+}
+static void carve_batch_work(Carver& c, BatchBufs& b) {  // S_WORK
+  carve_work(c, b.one);
+  b.work = c.take<uint8_t>(nmt_workspace_size(b.W / 2, b.n));
+}
+static void carve_batch_roots(Carver& c, BatchBufs& b) {  // S_ROOTS
+  carve_roots(c, b.one);
+  take_batch_results(c, b, &b.roots, &b.flags);
+}
+static void carve_batch_stage(Carver& c, BatchBufs& b) {  // the page-locked stage
+  carve_stage(c, b.one);
+  b.hidx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
+  take_batch_mask_list(c, b, &b.hmask, &b.hlist0);
+  take_batch_results(c, b, &b.hroots, &b.hflags);
+}
+static size_t carved(void (*walk)(Carver&, BatchBufs&), void* base, BatchBufs& b) {
+  Carver c(base);
+  walk(c, b);
+  return c.size();
+}
+constexpr struct {
+  int slot;
+  void (*walk)(Carver&, BatchBufs&);
+} kBatchSlots[] = {{S_IN, carve_batch_in},     {S_AUX, carve_batch_aux},     {S_MASK, carve_batch_mask},
+                   {S_WORK, carve_batch_work}, {S_ROOTS, carve_batch_roots}};
+
+// k = 32, 64, 128 and more than one square: the merged schedule; else square after square.
+static bool batch_merged(uint32_t k, uint32_t n) {
+  return n > 1 && (k == 32 || k == 64 || k == 128) && entries_fit(n, 2 * k);
+}
+
+static cel_status batch_bufs(cel_ctx* ctx, uint32_t k, uint32_t n, BatchBufs* b) {
+  hipError_t e = hipSuccess;
+  b->W = b->one.W = 2 * k;
+  b->n = n;
+  for (const auto& s : kBatchSlots) {
+    void* p = scratch(ctx, s.slot, carved(s.walk, nullptr, *b), &e);
+    if (!p) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+    carved(s.walk, p, *b);
+  }
+  b->res_bytes = (size_t)(reinterpret_cast<uint8_t*>(b->flags) - b->roots) + (size_t)n * 2 * b->W * 4;
+  if (!host_stage(ctx, carved(carve_batch_stage, nullptr, *b))) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
+  carved(carve_batch_stage, ctx->hstage, *b);
+  b->slot = 0;
+  b->main = ctx->stream;
+  b->side = ctx->sub[0];
+  b->ev_main = ctx->ev_repair_main;
+  b->ev_done = ctx->ev_repair_done;
+  return CEL_OK;
+}
+
+// `list` into the next entry-list slot, uploaded on stream s (upload_list's rule).
+static cel_status upload_entries(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, hipStream_t s,
+                                 int32_t** d_list) {
+  hipError_t e;
+  if (b.slot == kIdxSlots) {
+    if ((e = hipStreamSynchronize(b.main)) != hipSuccess || (e = hipStreamSynchronize(b.side)) != hipSuccess)
+      return hip_fail(ctx, e, "sync");
+    b.slot = 0;
+  }
+  int32_t* hidx = b.hidx + (size_t)b.slot * b.slot_len();
+  *d_list = b.idx + (size_t)b.slot * b.slot_len();
+  b.slot++;
+  std::memcpy(hidx, list.data(), list.size() * 4);
+  if ((e = hipMemcpyAsync(*d_list, hidx, list.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(ctx, e, "H2D");
+  return CEL_OK;
+}
+
+// A merged pass's decode on the main stream, then ev_main (solve_issue); `uploaded`: the
+// entries are on the device already (the first pass, in the masks' upload).
+static cel_status batch_solve_issue(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, Issued* out,
+                                    int32_t* uploaded = nullptr) {
+  const Range range("repair.batch.solve");
+  out->na = (uint32_t)list.size();
+  if (!out->na) return CEL_OK;
+  cel_status st;
+  if (uploaded) out->idx = uploaded;
+  else if ((st = upload_entries(ctx, b, list, b.main, &out->idx)) != CEL_OK) return st;
+  if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
+  hipError_t e;
+  if ((e = launch_rs_decode_in_squares(b.eds, b.mask, b.W, b.n, out->idx, out->na, ctx->tables.mul8, b.main)) !=
+          hipSuccess ||
+      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
+    return hip_fail(ctx, e, "solve");
+  return CEL_OK;
+}
+
+// Its encoding check on the side stream, after ev_main (solve_check).
+static cel_status batch_solve_check(cel_ctx* ctx, BatchBufs& b, const Issued& s) {
+  if (!s.na) return CEL_OK;
+  hipError_t e;
+  if ((e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess) return hip_fail(ctx, e, "event");
+  cel_status st;
+  if ((st = fuzz(ctx, b.side)) != CEL_OK) return st;
+  if ((e = launch_rs_check_axes_batch(b.eds, b.W / 2, b.n, s.idx, s.na, b.flags, b.side)) != hipSuccess)
+    return hip_fail(ctx, e, "encoding check");
+  return CEL_OK;
+}
+
+// Encoding check of complete axes (sanity, orthogonal completions) on the side stream (check_pass).
+static cel_status batch_check_pass(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, bool wait_main) {
+  const Range range("repair.batch.check");
+  if (list.empty()) return CEL_OK;
+  hipError_t e;
+  if (wait_main &&
+      ((e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess))
+    return hip_fail(ctx, e, "event");
+  int32_t* idx;
+  cel_status st;
+  if ((st = upload_entries(ctx, b, list, b.side, &idx)) != CEL_OK || (st = fuzz(ctx, b.side)) != CEL_OK) return st;
+  if ((e = launch_rs_check_axes_batch(b.eds, b.W / 2, b.n, idx, (uint32_t)list.size(), b.flags, b.side)) != hipSuccess)
+    return hip_fail(ctx, e, "encoding check");
+  return CEL_OK;
+}
+
+struct BatchOut {
+  cel_status* status;
+  int32_t* bad_axis;
+  int32_t* bad_index;
+  uint8_t* byz_shares;   // nullable, [n][W][512]
+  uint8_t* byz_present;  // nullable, [n][W]
+  RepairOut of(uint32_t i, uint32_t W) const {
+    return RepairOut{bad_axis ? bad_axis + i : nullptr, bad_index ? bad_index + i : nullptr,
+                     byz_shares ? byz_shares + (size_t)i * W * kShare : nullptr,
+                     byz_present ? byz_present + (size_t)i * W : nullptr};
+  }
+};
+
+// The squares resident at b.eds, masks hm ([n][W*W] bytes 0 / 1, updated per square as
+// repair_core leaves its own). CEL_OK when every square ran to an outcome (out.status).
+static cel_status repair_batch_core(cel_ctx* ctx, BatchBufs& b, std::vector<uint8_t>& hm, uint32_t k,
+                                    const uint8_t* row_roots, const uint8_t* col_roots, const BatchOut& out,
+                                    std::string* first_error) {
+  const uint32_t W = 2 * k, n = b.n;
+  const size_t cells = (size_t)W * W;
+  hipError_t e = hipSuccess;
+  cel_status st;
+  struct SideDrain {
+    hipStream_t side;
+    ~SideDrain() { (void)hipStreamSynchronize(side); }
+  } drain{b.side};
+  // every square's first row pass goes to the device before any bookkeeping exists; its
+  // entries ride in the masks' upload
+  const std::vector<int32_t> first = first_row_pass_batch(hm, n, k);
+  std::memcpy(b.hmask, hm.data(), n * cells);
+  if (!first.empty()) std::memcpy(b.hlist0, first.data(), first.size() * 4);
+  const size_t up_b = (size_t)(reinterpret_cast<uint8_t*>(b.hlist0) - b.hmask) + first.size() * 4;
+  if ((e = hipMemcpyAsync(b.mask, b.hmask, up_b, hipMemcpyHostToDevice, b.main)) != hipSuccess ||
+      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess ||
+      (e = hipMemsetAsync(b.flags, 0, (size_t)n * 2 * W * 4, b.side)) != hipSuccess)
+    return hip_fail(ctx, e, "H2D");
+  Issued prev;
+  if ((st = batch_solve_issue(ctx, b, first, &prev, b.list0)) != CEL_OK) return st;
+  bool first_issued = !first.empty();
+  std::unique_ptr<Range> plan_range(new Range("repair.batch.plan"));
+  BatchPasses bp(hm, n, k);
+  for (int is_col = 0; is_col < 2; is_col++)
+    if ((st = batch_check_pass(ctx, b, bp.sanity[is_col], true)) != CEL_OK) return st;
+  plan_range.reset();
+  // each pass's checks (its own, then the orthogonal completions) follow the next pass's decode
+  std::vector<int32_t> list, pending;
+  int is_col;
+  while (bp.next(&is_col, list)) {
+    if (first_issued) {  // the first row pass (the same entries, issued above)
+      first_issued = false;
+    } else {
+      Issued s1;
+      if ((st = batch_solve_issue(ctx, b, list, &s1)) != CEL_OK || (st = batch_solve_check(ctx, b, prev)) != CEL_OK ||
+          (st = batch_check_pass(ctx, b, pending, false)) != CEL_OK)
+        return st;
+      prev = s1;
+    }
+    const Range fill_range("repair.batch.fill");
+    bp.apply(pending);
+  }
+  // the last pass's checks beside the commit of all n squares, the join, one download
+  const size_t roots_b = (size_t)n * W * kNode;
+  if ((st = fuzz(ctx, b.main)) != CEL_OK || (st = batch_solve_check(ctx, b, prev)) != CEL_OK ||
+      (st = batch_check_pass(ctx, b, pending, false)) != CEL_OK)
+    return st;
+  if ((e = launch_commit(b.eds, k, n, b.roots, b.roots + roots_b, nullptr, nullptr, b.work, false, b.main)) != hipSuccess)
+    return hip_fail(ctx, e, "roots");
+  if ((e = hipEventRecord(b.ev_done, b.side)) != hipSuccess || (e = hipStreamWaitEvent(b.main, b.ev_done, 0)) != hipSuccess)
+    return hip_fail(ctx, e, "join");
+  if ((e = hipMemcpyAsync(b.hroots, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
+    return hip_fail(ctx, e, "D2H");
+  if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
+  // The verdicts, square by square. A replay (repair_exact) reuses the single-square prefix of
+  // the slots and of the stage, so the batch's results leave the stage first.
+  const std::vector<uint8_t> got_all(b.hroots, b.hroots + 2 * roots_b);
+  const std::vector<int32_t> flags_all(b.hflags, b.hflags + (size_t)n * 2 * W);
+  std::vector<uint8_t> got(2 * (size_t)W * kNode);
+  for (uint32_t i = 0; i < n; i++) {
+    SquarePasses& sq = bp.sq[i];
+    const uint8_t* const exp[2] = {row_roots + (size_t)i * W * kNode, col_roots + (size_t)i * W * kNode};
+    square_roots(got_all.data(), n, W, i, got.data());
+    std::vector<uint8_t> m(hm.begin() + (ptrdiff_t)(i * cells), hm.begin() + (ptrdiff_t)((i + 1) * cells));
+    const RepairOut o = out.of(i, W);
+    RepairBufs one = b.one;
+    one.eds = b.eds + i * cells * kShare;
+    cel_status code;
+    const long f = first_failure(sq.order.data(), sq.order.size(), {got.data(), kNode, RootRecords::BY_AXIS}, exp,
+                                 flags_all.data() + (size_t)i * 2 * W, W, &code);
+    if (f >= 0) {
+      const Check& c = sq.order[(size_t)f];
+      if (c.kind == Check::SANITY) {
+        st = fail_axis(ctx, one, m, o, code, c.is_col, c.idx, false);
+      } else {  // the order decides which axis fails first: this square again, alone, in rsmt2d's order
+        if ((st = repair_bufs(ctx, k, false, &one)) != CEL_OK) return st;
+        st = repair_exact(ctx, one, m, k, exp[0], exp[1], o);
+      }
+    } else if (!sq.solved()) {
+      rollback(m, W, sq.solves, sq.solves.size());
+      st = fail(ctx, CEL_EUNREPAIRABLE, "failed to solve data square");
+    } else {
+      std::fill(m.begin(), m.end(), (uint8_t)1);
+      st = CEL_OK;
+    }
+    if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
+    if (st != CEL_OK && first_error->empty()) *first_error = "square " + std::to_string(i) + ": " + ctx->last_error;
+    out.status[i] = st;
+    std::memcpy(hm.data() + i * cells, m.data(), cells);
+  }
+  return CEL_OK;
+}
+
+// Both batch entry points with ctx->mu held: the caller's device squares d_eds, or, with d_eds
+// null, the host squares h_eds through the ctx's own buffer.
+static cel_status repair_batch_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds, uint8_t* present, uint32_t n,
+                                      uint32_t k, uint32_t share_size, const uint8_t* row_roots,
+                                      const uint8_t* col_roots, const BatchOut& out) {
+  if ((!h_eds && !d_eds) || !present || !row_roots || !col_roots || !out.status)
+    return fail(ctx, CEL_EINVAL, "nil argument");
+  // the call's own arguments fail with CEL_EINVAL; the statuses of a repair are the squares'
+  cel_status st = validate_square(ctx, k, share_size);
+  if (st) return st == CEL_ECHUNK ? st : CEL_EINVAL;
+  if (n == 0) return CEL_OK;
+  const uint32_t W = 2 * k;
+  const size_t cells = (size_t)W * W, eds_b = cells * kShare;
+  std::string first_error;
+  if (!batch_merged(k, n)) {  // square after square through the single repair
+    for (uint32_t i = 0; i < n; i++) {
+      st = repair_locked(ctx, h_eds ? h_eds + i * eds_b : nullptr, d_eds ? static_cast<uint8_t*>(d_eds) + i * eds_b : nullptr,
+                         present + i * cells, k, share_size, row_roots + (size_t)i * W * kNode,
+                         col_roots + (size_t)i * W * kNode, out.of(i, W));
+      if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
+      if (st != CEL_OK && first_error.empty()) first_error = "square " + std::to_string(i) + ": " + ctx->last_error;
+      out.status[i] = st;
+    }
+    if (!first_error.empty()) ctx->last_error = first_error;
+    return CEL_OK;
+  }
+  for (int32_t* bad : {out.bad_axis, out.bad_index})
+    if (bad) std::fill(bad, bad + n, -1);
+  DeviceGuard g(ctx->device);
+  BatchBufs b{};
+  if ((st = batch_bufs(ctx, k, n, &b)) != CEL_OK) return st;
+  hipError_t e = hipSuccess;
+  b.eds = static_cast<uint8_t*>(d_eds);
+  if (!d_eds) {
+    if (!(b.eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, n * eds_b, &e)))) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+    if ((e = hipMemcpyAsync(b.eds, h_eds, n * eds_b, hipMemcpyHostToDevice, b.main)) != hipSuccess)
+      return hip_fail(ctx, e, "H2D");
+  }
+  std::vector<uint8_t> hm = normalise_mask(present, n * cells);
+  if ((st = repair_batch_core(ctx, b, hm, k, row_roots, col_roots, out, &first_error)) != CEL_OK) return st;
+  if (!d_eds) {  // every (partially) repaired square goes back, with the mask it is valid under
+    if ((e = hipMemcpyAsync(h_eds, b.eds, n * eds_b, hipMemcpyDeviceToHost, b.main)) != hipSuccess) return hip_fail(ctx, e, "D2H");
+    if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
+  }
+  std::memcpy(present, hm.data(), n * cells);
+  if (!first_error.empty()) ctx->last_error = first_error;
+  return CEL_OK;
+}
+
 }  // namespace
 
 cel_status cel_repair(cel_ctx* ctx, uint8_t* eds, uint8_t* present, uint32_t k, uint32_t share_size,
@@ -703,6 +1029,63 @@ cel_status cel_dev_repair(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t 
   if (!ctx) return CEL_EINVAL;
   std::lock_guard<std::mutex> lock(ctx->mu);
   return dev_repair_locked(ctx, d_eds, present, k, row_roots, col_roots, bad_axis, bad_index, byz_shares, byz_present);
+}
+
+size_t cel_dev_repair_batch_scratch_size(uint32_t k, uint32_t n) {
+  if (!k || (k & (k - 1)) || k > 512 || n == 0) return 0;
+  size_t total = 0;
+  if (!batch_merged(k, n)) {  // one square at a time
+    RepairBufs b{};
+    b.W = 2 * k;
+    for (auto walk : {carve_in, carve_aux, carve_mask, carve_work, carve_roots}) total += carved(walk, nullptr, b);
+    return total;
+  }
+  BatchBufs b{};
+  b.W = b.one.W = 2 * k;
+  b.n = n;
+  for (const auto& s : kBatchSlots) total += carved(s.walk, nullptr, b);
+  return total;
+}
+
+cel_status cel_dev_repair_batch(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t n, uint32_t k,
+                                const uint8_t* row_roots, const uint8_t* col_roots, cel_status* status,
+                                int32_t* bad_axis, int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present) {
+  if (!ctx) return CEL_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return repair_batch_locked(ctx, nullptr, d_eds, present, n, k, kShare, row_roots, col_roots,
+                             BatchOut{status, bad_axis, bad_index, byz_shares, byz_present});
+}
+
+cel_status cel_repair_batch(cel_ctx* ctx, uint8_t* eds, uint8_t* present, uint32_t n, uint32_t k, uint32_t share_size,
+                            const uint8_t* row_roots, const uint8_t* col_roots, cel_status* status, int32_t* bad_axis,
+                            int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present) {
+  if (!ctx) return CEL_EINVAL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  return repair_batch_locked(ctx, eds, nullptr, present, n, k, share_size, row_roots, col_roots,
+                             BatchOut{status, bad_axis, bad_index, byz_shares, byz_present});
+}
+
+cel_status cel_debug_repair_batch_plan(const uint8_t* present, uint32_t n, uint32_t k, int32_t* pass_dir,
+                                       uint32_t* pass_off, uint32_t* npasses, uint32_t* ent_square,
+                                       int32_t* ent_axis) {
+  if (!present || !pass_dir || !pass_off || !npasses || !ent_square || !ent_axis || !n || !k || (k & (k - 1)) ||
+      !entries_fit(n, 2 * k))
+    return CEL_EINVAL;
+  const std::vector<uint8_t> hm = normalise_mask(present, (size_t)n * 4 * k * k);
+  BatchPasses bp(hm, n, k);
+  const std::vector<BatchPass> passes = plan_batch(bp);
+  uint32_t at = 0;
+  for (size_t p = 0; p < passes.size(); p++) {
+    pass_dir[p] = passes[p].is_col;
+    pass_off[p] = at;
+    for (int32_t e : passes[p].entries) {
+      ent_square[at] = entry_square(e);
+      ent_axis[at++] = (int32_t)entry_axis(e);
+    }
+  }
+  pass_off[passes.size()] = at;
+  *npasses = (uint32_t)passes.size();
+  return CEL_OK;
 }
 
 }  // extern "C"

@@ -285,6 +285,14 @@ hipError_t launch_rs_decode_axis(uint8_t* shards, const uint8_t* present, uint32
 // in mask (W = 32 .. 256, the register decoder's range).
 hipError_t launch_rs_decode_in_square(uint8_t* eds, uint8_t* mask, uint32_t W, const int32_t* idx, int is_col,
                                       uint32_t naxes, const uint32_t* mul8, hipStream_t s);
+// The batch repair's passes over nsq squares back to back at eds ([nsq][W][W][512], masks
+// [nsq][W*W]), W = 64, 128, 256: nent entries, each an axis of one square with its direction
+// (repair_plan.hpp pack_entry). The decode as launch_rs_decode_in_square per entry; the
+// encoding check as launch_rs_check_axes per entry, into flags[square][direction][axis].
+hipError_t launch_rs_decode_in_squares(uint8_t* eds, uint8_t* masks, uint32_t W, uint32_t nsq, const int32_t* entries,
+                                       uint32_t nent, const uint32_t* mul8, hipStream_t s);
+hipError_t launch_rs_check_axes_batch(const uint8_t* eds, uint32_t k, uint32_t nsq, const int32_t* entries,
+                                      uint32_t nent, int32_t* flags, hipStream_t s);
 
 }  // namespace cel
 

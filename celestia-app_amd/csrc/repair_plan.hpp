@@ -1,8 +1,9 @@
 // The repair's host planner (api_repair.cpp): everything rsmt2d's Repair decides from the
 // presence mask alone. The pass-parallel schedule's bookkeeping (MaskBits), rsmt2d's own
 // sweep order (plan_sweeps), the log of checks both leave behind and its replay over the
-// roots and flags the device sends back. Plain C++ with no HIP in it:
-// tools/repair_plan_check.cpp includes this header alone and walks it on the host.
+// roots and flags the device sends back, and the merged schedule of a batch of squares
+// (BatchPasses). Plain C++ with no HIP in it: tools/repair_plan_check.cpp and
+// tools/repair_batch_plan_check.cpp include this header alone and walk it on the host.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -41,11 +42,11 @@ inline std::vector<uint8_t> normalise_mask(const uint8_t* present, size_t cells)
 
 // The rows the first pass solves (k <= known cells < 2k), ascending, from the byte mask
 // alone: the repair enqueues their decode before it builds the bitsets.
-inline std::vector<int32_t> first_row_pass(const std::vector<uint8_t>& hm, uint32_t k) {
+inline std::vector<int32_t> first_row_pass(const uint8_t* hm, uint32_t k) {
   const uint32_t W = 2 * k;
   std::vector<int32_t> first;
   for (uint32_t i = 0; i < W; i++) {  // hm bytes are 0 / 1: a word's popcount is its count
-    const uint8_t* r = hm.data() + (size_t)i * W;
+    const uint8_t* r = hm + (size_t)i * W;
     uint32_t c = 0;
     uint32_t j = 0;
     for (; j + 8 <= W; j += 8) {
@@ -57,6 +58,9 @@ inline std::vector<int32_t> first_row_pass(const std::vector<uint8_t>& hm, uint3
     if (c >= k && c < W) first.push_back((int32_t)i);
   }
   return first;
+}
+inline std::vector<int32_t> first_row_pass(const std::vector<uint8_t>& hm, uint32_t k) {
+  return first_row_pass(hm.data(), k);
 }
 
 // a[i] bit j <-> a[j] bit i
@@ -78,11 +82,12 @@ struct MaskBits {
   std::vector<uint64_t> bits[2];  // [is_col][axis * nw + word]
   std::vector<uint32_t> cnt[2];
   uint64_t total = 0;
-  MaskBits(const std::vector<uint8_t>& hm, uint32_t w) : W(w), nw((w + 63) / 64) {
+  MaskBits(const std::vector<uint8_t>& hm, uint32_t w) : MaskBits(hm.data(), w) {}
+  MaskBits(const uint8_t* hm, uint32_t w) : W(w), nw((w + 63) / 64) {
     const uint32_t P = nw * 64;  // padded to whole 64x64 tiles for the transpose
     std::vector<uint64_t> rows((size_t)P * nw, 0), cols((size_t)P * nw, 0);
     for (uint32_t i = 0; i < W; i++) {
-      const uint8_t* r = hm.data() + (size_t)i * W;
+      const uint8_t* r = hm + (size_t)i * W;
       for (uint32_t j = 0; j < W; j += 8) {
         uint64_t x = 0;
         const uint32_t n = W - j < 8 ? W - j : 8;
@@ -274,6 +279,143 @@ inline long first_failure(const Check* order, size_t n, const RootRecords& got, 
     if (*code != CEL_OK) return (long)t;
   }
   return -1;
+}
+
+// ------------------------------------------------------------------ batch of squares
+//
+// The repair of n squares in one call (cel_dev_repair_batch) merges their pass schedules by
+// round and direction: global pass (round r, rows) is every square's row list of round r, one
+// after another in square order, and likewise the columns. A square with nothing to solve in
+// a pass is absent from it, so each square's projection of the merged passes is its own
+// schedule, pass for pass, and the checks, the solve log and the rollback stay per square.
+
+// An entry of a merged pass, as the batch kernels read it (rs_decode_axis.hip, rs_axis.hip):
+// axis in bits 0..8, square in bits 9..29, direction in bit 30.
+constexpr uint32_t kEntryAxisBits = 9, kEntrySquareBits = 21;
+inline int32_t pack_entry(uint32_t square, uint32_t axis, int is_col) {
+  return (int32_t)(axis | (square << kEntryAxisBits) | ((uint32_t)(is_col != 0) << 30));
+}
+inline uint32_t entry_axis(int32_t e) { return (uint32_t)e & ((1u << kEntryAxisBits) - 1); }
+inline uint32_t entry_square(int32_t e) { return ((uint32_t)e >> kEntryAxisBits) & ((1u << kEntrySquareBits) - 1); }
+inline int entry_is_col(int32_t e) { return (int)(((uint32_t)e >> 30) & 1u); }
+inline bool entries_fit(uint32_t n, uint32_t W) { return W <= (1u << kEntryAxisBits) && n <= (1u << kEntrySquareBits); }
+
+// The first row pass of every square (first_row_pass per mask, packed): what the batch
+// enqueues before any square's bookkeeping exists. masks: [n][W * W] bytes 0 / 1.
+inline std::vector<int32_t> first_row_pass_batch(const std::vector<uint8_t>& masks, uint32_t n, uint32_t k) {
+  const size_t cells = (size_t)4 * k * k;
+  std::vector<int32_t> first;
+  for (uint32_t q = 0; q < n; q++) {
+    for (int32_t i : first_row_pass(masks.data() + q * cells, k)) first.push_back(pack_entry(q, (uint32_t)i, 0));
+  }
+  return first;
+}
+
+// One square's pass schedule as a stepper: the lists come from the counts, apply() is the
+// sequential view of the pass (fill_pass, log_pass), as repair_core takes them one by one.
+struct SquarePasses {
+  uint32_t k, W;
+  MaskBits mb;
+  std::vector<Check> order;
+  std::vector<Solve> solves;
+  std::vector<std::vector<int32_t>> by_solve;
+  SquarePasses(const uint8_t* hm, uint32_t k_) : k(k_), W(2 * k_), mb(hm, 2 * k_) {}
+  bool solved() const { return mb.total == (uint64_t)W * W; }
+  // preRepairSanityCheck: for i: row i, column i. Appends the checks; comp = the complete axes.
+  void sanity(std::vector<int32_t> comp[2]) {
+    for (uint32_t i = 0; i < W; i++)
+      for (int is_col = 0; is_col < 2; is_col++)
+        if (mb.cnt[is_col][i] == W) {
+          order.push_back({Check::SANITY, is_col, (int32_t)i, -1});
+          comp[is_col].push_back((int32_t)i);
+        }
+  }
+  void solvable(int is_col, std::vector<int32_t>& list) const {
+    list.clear();
+    for (uint32_t i = 0; i < W; i++)
+      if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) list.push_back((int32_t)i);
+  }
+  void apply(int is_col, const std::vector<int32_t>& list, std::vector<int32_t>& orth) {
+    mb.fill_pass(is_col, list, by_solve);
+    log_pass(is_col, list, by_solve, order, solves, orth);
+  }
+};
+
+// The merged schedule of n squares, pass by pass. next() gives the next non-empty global pass
+// from the counts alone (cheap: the caller enqueues its decode at once); apply() then runs
+// every listed square's bookkeeping and gives the orthogonal axes the pass completed, packed,
+// in direction !is_col. Serial per square.
+struct BatchPasses {
+  uint32_t n, k, W;
+  std::vector<SquarePasses> sq;
+  std::vector<int32_t> sanity[2];  // packed, by direction
+  BatchPasses(const std::vector<uint8_t>& masks, uint32_t n_, uint32_t k_) : n(n_), k(k_), W(2 * k_) {
+    const size_t cells = (size_t)W * W;
+    sq.reserve(n);
+    std::vector<int32_t> comp[2];
+    for (uint32_t q = 0; q < n; q++) {
+      sq.emplace_back(masks.data() + q * cells, k);
+      comp[0].clear();
+      comp[1].clear();
+      sq.back().sanity(comp);
+      for (int d = 0; d < 2; d++)
+        for (int32_t i : comp[d]) sanity[d].push_back(pack_entry(q, (uint32_t)i, d));
+    }
+    lists.resize(n);
+  }
+  // false: no square has anything left to solve (each is solved or stuck)
+  bool next(int* is_col, std::vector<int32_t>& entries) {
+    for (uint32_t tries = 0; tries < 2; tries++, dir ^= 1) {
+      entries.clear();
+      for (uint32_t q = 0; q < n; q++) {
+        lists[q].clear();
+        if (!sq[q].solved()) sq[q].solvable(dir, lists[q]);
+        for (int32_t i : lists[q]) entries.push_back(pack_entry(q, (uint32_t)i, dir));
+      }
+      if (!entries.empty()) {
+        *is_col = dir;
+        return true;
+      }
+    }
+    return false;
+  }
+  void apply(std::vector<int32_t>& orth) {
+    orth.clear();
+    std::vector<int32_t> o;
+    for (uint32_t q = 0; q < n; q++) {
+      if (lists[q].empty()) continue;
+      sq[q].apply(dir, lists[q], o);
+      for (int32_t j : o) orth.push_back(pack_entry(q, (uint32_t)j, !dir));
+    }
+    dir ^= 1;
+  }
+
+ private:
+  int dir = 0;                              // direction of the pass next() looks at first
+  std::vector<std::vector<int32_t>> lists;  // the pass next() gave, by square
+};
+
+// Square i's root records, [2][W] by (direction, axis) as first_failure reads them BY_AXIS, out
+// of the batch commit's: [n][W] row roots, then [n][W] column roots, kRoot bytes each.
+inline void square_roots(const uint8_t* all, uint32_t n, uint32_t W, uint32_t i, uint8_t* out) {
+  const size_t axis_b = (size_t)W * kRoot;
+  std::memcpy(out, all + i * axis_b, axis_b);
+  std::memcpy(out + axis_b, all + ((size_t)n + i) * axis_b, axis_b);
+}
+
+// The whole merged schedule at once (cel_debug_repair_batch_plan, tools/repair_batch_plan_check.cpp).
+struct BatchPass {
+  int is_col;
+  std::vector<int32_t> entries, orth;
+};
+inline std::vector<BatchPass> plan_batch(BatchPasses& bp) {
+  std::vector<BatchPass> passes;
+  BatchPass p;
+  while (bp.next(&p.is_col, p.entries)) {
+    bp.apply(p.orth);
+    passes.push_back(p);
+  }
+  return passes;
 }
 
 }  // namespace repair

@@ -294,6 +294,36 @@ __global__ __launch_bounds__(256, 3) void k_rs_check_axes(const uint8_t* __restr
   if (__any(diff != 0u) && lane == 0) atomicOr(flags + ax, 1);
 }
 
+// The same over listed axes of nsq squares back to back at `eds` (cel_dev_repair_batch). An
+// entry names its axis (bits 0..8), its square (bits 9..29) and its direction (bit 30), as the
+// batch decode's (repair_plan.hpp pack_entry); a mismatch sets flags[square][direction][axis].
+// The square's base is a 64-bit wave-uniform offset, offsets inside it 32-bit as above.
+template <int LOGK>
+__global__ __launch_bounds__(256, 3) void k_rs_check_axes_batch(const uint8_t* __restrict__ eds,
+                                                                const int32_t* __restrict__ entries, uint32_t nent,
+                                                                int32_t* __restrict__ flags) {
+  constexpr int K = 1 << LOGK;
+  constexpr uint32_t W = 2 * K, nslice = kShare / 256;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+  if (tile >= nent * nslice) return;
+  const uint32_t y = tile % nslice, a = tile / nslice;
+  const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane(entries[a]);
+  const uint32_t ax = e & 0x1FFu, sq = (e >> 9) & 0x1FFFFFu, is_col = (e >> 30) & 1u;
+  const uint64_t base = (uint64_t)sq * W * W * kShare + (is_col ? (uint64_t)ax * kShare : (uint64_t)ax * W * kShare);
+  const uint32_t stride = is_col ? W * kShare : kShare;
+  const auto rin = rsrc(eds + base + (uint64_t)y * 256u);
+  const uint32_t lo = lane * 4u;
+  uint32_t w[K];
+#pragma unroll
+  for (int i = 0; i < K; i++) w[i] = __builtin_amdgcn_raw_buffer_load_b32(rin, lo, (uint32_t)i * stride, 0);
+  transform_hyb<K>(w);
+  uint32_t diff = 0;
+#pragma unroll
+  for (int i = 0; i < K; i++) diff |= w[i] ^ __builtin_amdgcn_raw_buffer_load_b32(rin, lo, (uint32_t)(K + i) * stride, 0);
+  if (__any(diff != 0u) && lane == 0) atomicOr(flags + ((uint64_t)sq * 2 + is_col) * W + ax, 1);
+}
+
 }  // namespace ax
 
 // Byte offsets must fit the 32-bit buffer offsets: (n - 1) * shard stride + len < 2 GiB.
@@ -347,6 +377,22 @@ hipError_t launch_rs_check_axes(const uint8_t* eds, uint32_t k, const int32_t* i
     case 32: hipLaunchKernelGGL(ax::k_rs_check_axes<5>, grid, dim3(256), 0, s, eds, W, idx, is_col, naxes, flags); break;
     case 64: hipLaunchKernelGGL(ax::k_rs_check_axes<6>, grid, dim3(256), 0, s, eds, W, idx, is_col, naxes, flags); break;
     case 128: hipLaunchKernelGGL(ax::k_rs_check_axes<7>, grid, dim3(256), 0, s, eds, W, idx, is_col, naxes, flags); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_check_axes_batch(const uint8_t* eds, uint32_t k, uint32_t nsq, const int32_t* entries,
+                                      uint32_t nent, int32_t* flags, hipStream_t s) {
+  const uint32_t W = 2 * k;
+  if ((uint64_t)(W - 1) * W * kShare + kShare >= 0x7fffffffull || nsq > (1u << 21)) return hipErrorInvalidValue;
+  if (nent == 0) return hipSuccess;
+  if ((uint64_t)nent * (kShare / 256) > 0xFFFFFFF0ull) return hipErrorInvalidValue;
+  const dim3 grid((nent * (kShare / 256) + 3) / 4);
+  switch (k) {
+    case 32: hipLaunchKernelGGL(ax::k_rs_check_axes_batch<5>, grid, dim3(256), 0, s, eds, entries, nent, flags); break;
+    case 64: hipLaunchKernelGGL(ax::k_rs_check_axes_batch<6>, grid, dim3(256), 0, s, eds, entries, nent, flags); break;
+    case 128: hipLaunchKernelGGL(ax::k_rs_check_axes_batch<7>, grid, dim3(256), 0, s, eds, entries, nent, flags); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

@@ -99,7 +99,13 @@ __device__ __forceinline__ void cross_fft(uint32_t& v, bool hi, uint32_t m7, uin
 // `shards` (a row if !is_col, else a column: shard stride len or W * len) with its
 // presence in the square's mask `present`; in-square decodes store the erased cells
 // straight into the square and mark the axis present (the repair's gather and scatter).
-template <int LOGN>
+//
+// BATCH (in-square only, n squares of W x W cells back to back at `shards`, their masks back to
+// back at `present`): entry = axis in bits 0..8, square in bits 9..29, direction in bit 30
+// (repair_plan.hpp pack_entry). The workgroup moves `shards` and `present` to its square by a
+// 64-bit wave-uniform offset; every offset inside the square stays a 32-bit buffer offset.
+// The single-square instantiations (BATCH = false) compile to what they did without it.
+template <int LOGN, bool BATCH = false>
 __global__ __launch_bounds__(256, 2) void k_rs_decode_axis(uint8_t* __restrict__ shards,
                                                            uint8_t* __restrict__ present, uint32_t len,
                                                            const uint32_t* __restrict__ mul8,
@@ -122,8 +128,13 @@ __global__ __launch_bounds__(256, 2) void k_rs_decode_axis(uint8_t* __restrict__
   if (idx) {
     // is_col < 0: each entry names its own direction (bit 30 set = column)
     const uint32_t e = (uint32_t)idx[blockIdx.x];
-    const uint32_t ax = e & 0x3FFFFFFFu;
-    if (is_col < 0) is_col = (int)((e >> 30) & 1u);
+    const uint32_t ax = e & (BATCH ? 0x1FFu : 0x3FFFFFFFu);
+    if (BATCH || is_col < 0) is_col = (int)((e >> 30) & 1u);
+    if constexpr (BATCH) {
+      const uint64_t sq = (e >> 9) & 0x1FFFFFu;
+      shards += sq * W * W * len;
+      present += sq * W * W;
+    }
     axis = shards + (is_col ? (uint64_t)ax * len : (uint64_t)ax * W * len);
     sst = is_col ? W * len : len;
     pa = present + (is_col ? (uint64_t)ax : (uint64_t)ax * W);
@@ -324,6 +335,15 @@ __global__ __launch_bounds__(256, 2) void k_rs_decode_axis(uint8_t* __restrict__
   });
 }
 
+// One launch over listed axes of many squares (cel_dev_repair_batch); is_col is unused there.
+template <int LOGN>
+hipError_t launch_batch(uint8_t* eds, uint8_t* masks, uint32_t nent, const uint32_t* mul8, const int32_t* entries,
+                        hipStream_t s) {
+  hipLaunchKernelGGL((k_rs_decode_axis<LOGN, true>), dim3(nent, 1), dim3(256), 0, s, eds, masks, (uint32_t)kShare, mul8,
+                     entries, 1u << LOGN, 0);
+  return hipGetLastError();
+}
+
 template <int LOGN>
 hipError_t launch(uint8_t* shards, uint8_t* present, uint32_t naxes, uint32_t len, const uint32_t* mul8,
                   const int32_t* idx, uint32_t W, int is_col, hipStream_t s) {
@@ -366,6 +386,21 @@ hipError_t launch_rs_decode_in_square(uint8_t* eds, uint8_t* mask, uint32_t W, c
   if (!rs_decode_axis_supported(W, kShare) || (uint64_t)W * W * kShare >= 0x7fffffffull) return hipErrorInvalidValue;
   if (naxes == 0) return hipSuccess;
   return decode_axes(eds, mask, naxes, W, kShare, mul8, idx, W, is_col, s);
+}
+
+hipError_t launch_rs_decode_in_squares(uint8_t* eds, uint8_t* masks, uint32_t W, uint32_t nsq, const int32_t* entries,
+                                       uint32_t nent, const uint32_t* mul8, hipStream_t s) {
+  static_assert(kShare <= 4 * 128, "in-square decode: one y-block per axis");
+  // the entry format: axis below 2^9, square below 2^21; offsets inside a square as above
+  if (!rs_decode_axis_supported(W, kShare) || (uint64_t)W * W * kShare >= 0x7fffffffull || nsq > (1u << 21))
+    return hipErrorInvalidValue;
+  if (nent == 0) return hipSuccess;
+  switch (W) {
+    case 64: return dx::launch_batch<6>(eds, masks, nent, mul8, entries, s);
+    case 128: return dx::launch_batch<7>(eds, masks, nent, mul8, entries, s);
+    case 256: return dx::launch_batch<8>(eds, masks, nent, mul8, entries, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace cel

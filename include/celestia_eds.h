@@ -360,6 +360,44 @@ cel_status cel_debug_schedule_fuzz(cel_ctx* ctx, uint64_t seed, uint32_t max_us)
 cel_status cel_debug_repair_plan(const uint8_t* present, uint32_t k, int32_t* solve_axis, int32_t* solve_index,
                                  int32_t* solve_level, uint32_t* nsolves, int32_t* solved);
 
+/* The repair of n squares of one k in one call (a node catching up over a range of heights):
+ * d_eds is [n][2k][2k][512] on ctx's device, filled in place; present [n][2k*2k], the roots
+ * [n][2k][90] and the outputs are host memory. For k = 32, 64, 128 and n > 1 the squares'
+ * crossword passes are merged (every solvable row of every square in one decode launch, then
+ * every solvable column, ...), one commit gives all roots and one copy brings the results
+ * back; any other k, and n = 1, runs cel_dev_repair square after square. Per square i,
+ * status[i], present[i], bad_axis[i], bad_index[i], byz_shares[i] ([2k][512]), byz_present[i]
+ * ([2k]) and every cell present[i] vouches for are what cel_dev_repair gives for that square
+ * alone; one square's failure changes nothing about another. status is required; bad_axis,
+ * bad_index, byz_shares and byz_present are nullable.
+ * Returns CEL_OK whenever every square ran to one of CEL_OK, CEL_EBYZANTINE, CEL_EBADROOT,
+ * CEL_EUNREPAIRABLE (in status[]; cel_last_error then holds the first failing square's
+ * message, prefixed "square i: "). CEL_EINVAL (a nil argument, k not a power of two or above
+ * 512), CEL_ENOMEM and CEL_EDEVICE are the call's own; n = 0 is CEL_OK and touches nothing.
+ * Synchronous. */
+cel_status cel_dev_repair_batch(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t n, uint32_t k,
+                                const uint8_t* row_roots, const uint8_t* col_roots, cel_status* status,
+                                int32_t* bad_axis, int32_t* bad_index, uint8_t* byz_shares,
+                                uint8_t* byz_present);
+/* Device scratch (bytes) the ctx holds after cel_dev_repair_batch(k, n), beside the caller's
+ * squares: masks, flags, roots, entry lists and the commit workspace of n squares, on top of
+ * one square's repair buffers. It grows with n; 0 for a k the repair does not take or n = 0. */
+size_t cel_dev_repair_batch_scratch_size(uint32_t k, uint32_t n);
+/* The same over host squares eds [n][2k][2k][share_size], in and out (uploaded before,
+ * downloaded after, through n squares of ctx scratch on top of the size above). */
+cel_status cel_repair_batch(cel_ctx* ctx, uint8_t* eds, uint8_t* present, uint32_t n, uint32_t k,
+                            uint32_t share_size, const uint8_t* row_roots, const uint8_t* col_roots,
+                            cel_status* status, int32_t* bad_axis, int32_t* bad_index,
+                            uint8_t* byz_shares, uint8_t* byz_present);
+/* Tests only, host-only (no device): the merged pass schedule of n presence masks
+ * ([n][2k*2k], k <= 256). Global pass p has direction pass_dir[p] (0 rows, 1 columns) and
+ * the entries [pass_off[p], pass_off[p + 1]): entry e is axis ent_axis[e] of square
+ * ent_square[e], squares in ascending order, a square's axes ascending. pass_dir holds up to
+ * 8k passes, pass_off one more, the entries up to n * 4k (each axis is solved at most once). */
+cel_status cel_debug_repair_batch_plan(const uint8_t* present, uint32_t n, uint32_t k, int32_t* pass_dir,
+                                       uint32_t* pass_off, uint32_t* npasses, uint32_t* ent_square,
+                                       int32_t* ent_axis);
+
 /* ------------------------------------------------------- exported trees, proofs
  * pkg/proof (proof.go:78-202, row_proof.go, share_proof.go) and the subtree-root
  * cacher (pkg/inclusion/nmt_caching.go:96-124) need inner nodes, which the reference
