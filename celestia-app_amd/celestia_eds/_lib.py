@@ -17,6 +17,7 @@ OK, EINVAL, ENOTPOW2, ECHUNK, ETOOBIG, EORDER, ETOOFEW, EBYZANTINE, EUNREPAIRABL
     ESHORT, EPUSHPAST, EBADROOT, ENODATA = range(15)
 FLAG_ORDER_CHECK = 0x1
 NS_INCLUSION, NS_ABSENCE = 0, 1
+BEFP_NOT_FRAUD, BEFP_FRAUD, BEFP_BAD_SHARE, BEFP_TOO_FEW, BEFP_MALFORMED = range(5)  # fraud-proof verdicts
 BLOB_EVERSION, BLOB_ENOSTART, BLOB_ESHORT = 1, 2, 3  # range status codes of the blob parser
 TX_EVERSION, TX_ENAMESPACE, TX_ERESERVED, TX_EVARINT = 1, 2, 3, 4  # of the compact share parser
 TX_FHINTS = 1  # range flag: the reserved bytes disagree with the sequential parse
@@ -57,6 +58,7 @@ EXPORTS = [
     "cel_dev_blobs_workspace_size", "cel_dev_blobs_plan", "cel_dev_blobs_emit", "cel_blobs_by_range",
     "cel_namespace_ods_ranges",
     "cel_dev_txs_workspace_size", "cel_dev_txs_plan", "cel_dev_txs_emit", "cel_txs_by_range",
+    "cel_befp_verify_batch", "cel_dev_befp_build", "cel_befp_build",
 ]
 
 _lib = None
@@ -180,6 +182,9 @@ def load():
             "cel_dev_txs_plan": (i32, [P, P, u32, u32, P, P, P, P, P, P, P, P]),
             "cel_dev_txs_emit": (i32, [P, P, u32, u64, P, P, P, P, P]),
             "cel_txs_by_range": (i32, [P, P, u32, u32, P, P, u64, u64, P, P, P, P, P, P, P]),
+            "cel_befp_verify_batch": (i32, [P, u32, u32] + [P] * 12),
+            "cel_dev_befp_build": (i32, [P, P, P, u32, P, P, u32, u32, P, P, P, P, P]),
+            "cel_befp_build": (i32, [P, P, P, u32, P, P, u32, u32, P, P, P, P, P]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(l, name)

@@ -31,7 +31,7 @@ Row, Col = 0, 1  # rsmt2d.Axis
 class ErrByzantineData(CelError):
     """rsmt2d *ErrByzantineData{Axis, Index, Shares}: Shares lists the axis's 2k shares,
     None where the repair did not know the cell (celestia-node builds bad-encoding fraud
-    proofs from them, specs/src/specs/fraud_proofs.md:3-13)."""
+    proofs from them, specs/src/specs/fraud_proofs.md:3-13; here fraud.CreateBadEncodingProof)."""
 
     def __init__(self, axis, index, message, shares=None):
         super().__init__(_lib.EBYZANTINE, message)

@@ -480,6 +480,80 @@ cel_status cel_repair_samples(cel_ctx* ctx, uint32_t k, const uint8_t* row_roots
                               uint8_t* ok_out, uint8_t* eds_out, uint8_t* present_out, int32_t* bad_axis,
                               int32_t* bad_index, uint8_t* byz_shares, uint8_t* byz_present);
 
+/* ------------------------------------------------- bad-encoding fraud proofs
+ * What a node does with CEL_EBYZANTINE (specs/src/specs/fraud_proofs.md:3-13, networking.md
+ * "Invalid Erasure Coding", types.proto BadEncodingFraudProof; celestia-node share/eds/byzantine):
+ * it builds a proof that axis (axis, index) of the square is badly encoded (axis 0 = row, 1 =
+ * column), and a peer checks such a proof against the square's 2k row roots and 2k column
+ * roots. A proof carries entries: a position in the accused axis, the 512-byte share there, a
+ * single-leaf nmt proof of it and an entry_axis that says which tree the proof is in, in the
+ * convention of cel_dev_place_samples. The cell is (index, position) of an accused row,
+ * (position, index) of an accused column; entry_axis 0 proves it at leaf col of row_roots[row],
+ * entry_axis 1 at leaf row of col_roots[col], the namespace by the wrapper's rule
+ * (nmt_wrapper.go:100-107). The reference specification's form (shares proved in the accused
+ * root) and celestia-node's (in the orthogonal roots) are both entries of this kind.
+ *
+ * The verdict of one proof, one byte, the rule applied in this order (celestia-node's
+ * BadEncodingProof.Validate):
+ *   CEL_BEFP_MALFORMED  axis > 1, index >= 2k, an entry's position >= 2k or entry_axis > 1, or
+ *                       two entries with one position.
+ *   CEL_BEFP_TOO_FEW    fewer than k entries.
+ *   CEL_BEFP_BAD_SHARE  an entry's nmt proof does not verify (a wrong node count is such an
+ *                       entry, not an error of the call).
+ *   otherwise the axis is rebuilt: the entries at their positions, every other shard absent,
+ *   Codec.Decode, the parity half replaced by Codec.Encode(data half), and the root taken as
+ *   the wrapper tree of axis `index` (no push-order check, as the repair's root check).
+ *   CEL_BEFP_FRAUD      that root differs from the accused root (row_roots[index] or
+ *                       col_roots[index]).
+ *   CEL_BEFP_NOT_FRAUD  it is the accused root.
+ * The rule cannot prove fraud where the accused root is honest and the corrupt cell is one its
+ * orthogonal root does not commit to: no entry for that cell verifies, and the others rebuild
+ * the honest axis. */
+#define CEL_BEFP_NOT_FRAUD 0
+#define CEL_BEFP_FRAUD 1
+#define CEL_BEFP_BAD_SHARE 2
+#define CEL_BEFP_TOO_FEW 3
+#define CEL_BEFP_MALFORMED 4
+/* n proofs for squares of one k, everything in host memory (proofs arrive from peers). Proof i
+ * accuses (axes[i], index[i]) and holds the entries ent_off[i]..ent_off[i+1]; entry e is
+ * positions[e], ent_axes[e], the share shares[512*e..] and the 90-byte nodes
+ * node_off[e]..node_off[e+1] of `nodes` in nmt order (the layout cel_nmt_verify_batch reads;
+ * node_off has ent_off[n] + 1 values). row_roots / col_roots: [n][2k][90], proof i's square.
+ * verdict_out[n]; rebuilt_roots_out [n][90] (nullable): the rebuilt axis's root where the
+ * verdict is CEL_BEFP_FRAUD or CEL_BEFP_NOT_FRAUD, zeros elsewhere. One proof's verdict never
+ * depends on another's, and nothing in a proof makes the call fail. MALFORMED and TOO_FEW are
+ * decided on the host and take no device work; the rest is one upload, one chain of kernels
+ * on the ctx's stream (entries verified, placed into dense axes, decoded, re-encoded, hashed,
+ * compared) and one download. Synchronous.
+ * CEL_EINVAL: a nil argument, decreasing offsets, k not a power of two or above 512, or more
+ * than 2^31 entries or nodes; CEL_ENOMEM; CEL_EDEVICE. n = 0 is CEL_OK. */
+cel_status cel_befp_verify_batch(cel_ctx* ctx, uint32_t n, uint32_t k, const uint8_t* axes,
+                                 const uint32_t* index, const uint64_t* ent_off,
+                                 const uint32_t* positions, const uint8_t* ent_axes,
+                                 const uint8_t* shares, const uint8_t* nodes, const uint64_t* node_off,
+                                 const uint8_t* row_roots, const uint8_t* col_roots,
+                                 uint8_t* verdict_out, uint8_t* rebuilt_roots_out);
+/* The producer, over the square a cel_dev_repair left resident (d_eds: 2k*2k*512 bytes, 16-byte
+ * aligned; present: host, 2k*2k, the mask the repair returned) and the axis it reported
+ * (bad_axis, bad_index). Position j of that axis becomes an entry when its cell is known, the
+ * orthogonal axis j (column j of a row, row j of a column) is complete in present, and that
+ * axis's root, recomputed on the device, equals its root in the header: a cell corrupted after
+ * the roots were made gives no entry that would fail. Entry e, positions ascending:
+ * positions_out[e], ent_axes_out[e] (the orthogonal direction), shares_out[512*e..] and its
+ * log2(2k) nodes at nodes_out[90*log2(2k)*e..], the bytes cel_nmt_prove_range gives on that
+ * tree. The outputs hold 2k entries; *count_out is how many there are. Fewer than k is
+ * CEL_OK with the count (an outcome: the caller adds sample proofs it holds). Synchronous.
+ * CEL_EINVAL: a nil argument, k not a power of two or above 512, bad_axis > 1, bad_index >= 2k. */
+cel_status cel_dev_befp_build(cel_ctx* ctx, const void* d_eds, const uint8_t* present, uint32_t k,
+                              const uint8_t* row_roots, const uint8_t* col_roots, uint32_t bad_axis,
+                              uint32_t bad_index, uint32_t* positions_out, uint8_t* ent_axes_out,
+                              uint8_t* shares_out, uint8_t* nodes_out, uint32_t* count_out);
+/* The same over a square in host memory (eds: 2k*2k*512, as cel_repair leaves it). */
+cel_status cel_befp_build(cel_ctx* ctx, const uint8_t* eds, const uint8_t* present, uint32_t k,
+                          const uint8_t* row_roots, const uint8_t* col_roots, uint32_t bad_axis,
+                          uint32_t bad_index, uint32_t* positions_out, uint8_t* ent_axes_out,
+                          uint8_t* shares_out, uint8_t* nodes_out, uint32_t* count_out);
+
 /* ------------------------------------------------- proofs in batches, tree index
  * nmt ProveRange (nmt v0.22.0 [dep], as pkg/proof/proof.go:190 calls it per row) for many
  * requests over one resident square: the range proofs of ShareProofs and of sampled cells, in
