@@ -19,8 +19,6 @@ using namespace cel;
 using namespace cel::abi;
 using namespace cel::repair;
 
-extern "C" {
-
 // ------------------------------------------------------------------- repair
 
 // rsmt2d v0.14.0 ExtendedDataSquare.Repair [dep] (extendeddatacrossword.go), with the
@@ -35,39 +33,55 @@ namespace {
 // serialised the host against the stream). Slots wrap with one stream sync.
 constexpr uint32_t kIdxSlots = 64;
 
-struct RepairBufs {
-  uint32_t W;
-  uint8_t* eds;
-  uint8_t* mask;
-  int32_t* list0;     // the first pass's axis list, right after the mask (one upload for both)
+// What the pass schedule works on, of one square (RepairBufs) or of the n squares of a merged
+// batch (BatchBufs): a list slot holds a pass of either, up to n * W entries.
+struct PassBufs {
+  uint32_t W, n = 1;
+  uint8_t* eds;       // [n][W][W][512]
+  uint8_t* mask;      // [n][W*W]
+  int32_t* list0;     // the first pass's list, right after the masks (one upload for both)
+  uint8_t* work;      // NMT workspace of the n-square commit (one square: or repair_exact's axes roots)
+  uint8_t* roots;     // [n][W][90] row roots, [n][W][90] column roots, then the flags
+  int32_t* flags;     // [n][2][W] encoding-check flags by (square, direction, axis), right after the roots
+  uint8_t* hroots;    // page-locked copy of roots + flags (one D2H of res_bytes at the end)
+  int32_t* hflags;
+  size_t res_bytes;
+  int32_t* idx;       // [kIdxSlots][n*W] device lists
+  int32_t* hidx;      // [kIdxSlots][n*W] page-locked staging of the same
+  uint8_t* hmask;     // page-locked staging of the masks, then of the first list
+  int32_t* hlist0;
+  uint32_t slot;      // next free slot
+  // Two streams: the solve chain runs on `main`; every re-encode check (of the solved axes,
+  // the sanity and the orthogonal checks) runs on `side`, off the chain's critical path: its
+  // outcome is only read at the end.
+  hipStream_t main, side;
+  hipEvent_t ev_main;  // the squares after the main stream's latest pass
+  hipEvent_t ev_done;  // the side stream's last check
+  size_t slot_len() const { return (size_t)n * W; }
+};
+
+// One square, any k: with the dense path's buffers (gather -> decode -> scatter where no
+// in-square kernel exists) and repair_exact's.
+struct RepairBufs : PassBufs {
   uint8_t* dense[2];  // gathered axes of the solve passes, alternating (main stream)
   uint8_t* dmask;
   uint8_t* dchk;      // gathered axes of the check passes (side stream)
   uint8_t* dmask_chk;
   uint8_t* tmp;       // re-encoded parity halves (side stream)
-  uint8_t* work;      // NMT workspace of the final verification, or repair_exact's axes roots
-  uint32_t* rec;      // [2][W][kNodeWords] repair_exact's root records, in the same slot
-  uint8_t* roots;     // [2][W][90] row then column roots of the final verification, then flags
-  int32_t* flags;     // [2][W] encoding-check flags by (direction, axis), right after the roots
-  uint8_t* hroots;    // page-locked copy of roots + flags (one D2H of res_bytes at the end)
-  int32_t* hflags;
-  size_t res_bytes;
-  int32_t* idx;       // [kIdxSlots][W] device axis lists
-  int32_t* hidx;      // [kIdxSlots][W] page-locked staging of the same
-  uint8_t* hmask;     // [W][W] page-locked staging of the presence mask, then of the first list
-  int32_t* hlist0;
-  uint32_t slot;      // next free slot
+  uint32_t* rec;      // [2][W][kNodeWords] repair_exact's root records, in work's slot
   uint32_t solves;    // solve passes so far (which dense buffer is next)
-  // Two streams: the solve chain (gather -> decode -> scatter) runs on `main`; every
-  // re-encode check (of the solved axes, the sanity and the orthogonal checks) runs on
-  // `side`, off the chain's critical path: its outcome is only read at the end.
-  hipStream_t main, side;
-  hipEvent_t ev_main;     // the square after the main stream's latest pass
   hipEvent_t ev_side[2];  // the side stream is done with dense[i]
-  hipEvent_t ev_done;     // the side stream's last check
 };
 
-// The layout of each scratch slot and of the page-locked stage, one walk per buffer (b.W
+// Every scratch slot and the page-locked stage of a batch start with the single-square layout
+// (the same walks), the batch's regions after it: a square whose SOLVE or ORTH check fails is
+// replayed alone by repair_exact through a RepairBufs whose eds is that square's slice of the
+// batch, without a reallocation under the batch's buffers.
+struct BatchBufs : PassBufs {
+  RepairBufs one;  // the single-square prefix of every slot (eds, streams and events unset)
+};
+
+// The layout of each scratch slot and of the page-locked stage, one walk per buffer (W and n
 // set). carved() runs a walk: on a null base it gives the size to allocate, on the
 // allocation the pointers into it.
 static void carve_in(Carver& c, RepairBufs& b) {  // S_IN
@@ -77,23 +91,23 @@ static void carve_aux(Carver& c, RepairBufs& b) {  // S_AUX
   b.tmp = c.take<uint8_t>((size_t)b.W * b.W * kShare / 2);
   b.idx = c.take<int32_t>((size_t)kIdxSlots * b.W * 4);
 }
-// The presence mask, then the first pass's axis list directly after it: one upload carries
+// The presence masks, then the first pass's list directly after them: one upload carries
 // both, so the device buffer and the stage take them by the same walk.
-static void take_mask_list(Carver& c, uint32_t W, uint8_t** mask, int32_t** list0) {
-  *mask = c.take<uint8_t>((size_t)W * W);
-  *list0 = c.take<int32_t>((size_t)W * 4);
+static void take_mask_list(Carver& c, uint32_t n, uint32_t W, uint8_t** mask, int32_t** list0) {
+  *mask = c.take<uint8_t>((size_t)n * W * W);
+  *list0 = c.take<int32_t>((size_t)n * W * 4);
 }
 static void carve_mask(Carver& c, RepairBufs& b) {  // S_MASK
-  take_mask_list(c, b.W, &b.mask, &b.list0);
+  take_mask_list(c, 1, b.W, &b.mask, &b.list0);
   for (uint8_t** p : {&b.dmask, &b.dmask_chk}) *p = c.take<uint8_t>((size_t)b.W * b.W);
 }
-// Every root of the square, then the flags directly after them: one download (res_bytes,
+// Every root of the squares, then the flags directly after them: one download (res_bytes,
 // from the first root to the last flag) brings both back, into the same walk of the stage.
-static void take_results(Carver& c, uint32_t W, uint8_t** roots, int32_t** flags) {
-  *roots = c.take<uint8_t>(2 * (size_t)W * kNode);
-  *flags = c.take<int32_t>(2 * (size_t)W * 4);
+static void take_results(Carver& c, uint32_t n, uint32_t W, uint8_t** roots, int32_t** flags) {
+  *roots = c.take<uint8_t>((size_t)n * 2 * W * kNode);
+  *flags = c.take<int32_t>((size_t)n * 2 * W * 4);
 }
-static void carve_roots(Carver& c, RepairBufs& b) { take_results(c, b.W, &b.roots, &b.flags); }  // S_ROOTS
+static void carve_roots(Carver& c, RepairBufs& b) { take_results(c, 1, b.W, &b.roots, &b.flags); }  // S_ROOTS
 // repair_exact's axes-roots workspace of one direction's 2k axes, then, after it, the root
 // records of both directions; the whole-square commit's workspace lies over the two.
 static void carve_work(Carver& c, RepairBufs& b) {  // S_WORK
@@ -103,18 +117,81 @@ static void carve_work(Carver& c, RepairBufs& b) {  // S_WORK
 }
 static void carve_stage(Carver& c, RepairBufs& b) {  // the page-locked stage
   b.hidx = c.take<int32_t>((size_t)kIdxSlots * b.W * 4);
-  take_mask_list(c, b.W, &b.hmask, &b.hlist0);  // hmask followed by its list
-  take_results(c, b.W, &b.hroots, &b.hflags);
+  take_mask_list(c, 1, b.W, &b.hmask, &b.hlist0);  // hmask followed by its list
+  take_results(c, 1, b.W, &b.hroots, &b.hflags);
 }
-static size_t carved(void (*walk)(Carver&, RepairBufs&), void* base, RepairBufs& b) {
+static void carve_batch_in(Carver& c, BatchBufs& b) { carve_in(c, b.one); }  // S_IN: the replay's alone
+static void carve_batch_aux(Carver& c, BatchBufs& b) {                       // S_AUX
+  carve_aux(c, b.one);
+  b.idx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
+}
+static void carve_batch_mask(Carver& c, BatchBufs& b) {  // S_MASK
+  carve_mask(c, b.one);
+  take_mask_list(c, b.n, b.W, &b.mask, &b.list0);
+}
+static void carve_batch_work(Carver& c, BatchBufs& b) {  // S_WORK
+  carve_work(c, b.one);
+  b.work = c.take<uint8_t>(nmt_workspace_size(b.W / 2, b.n));
+}
+static void carve_batch_roots(Carver& c, BatchBufs& b) {  // S_ROOTS
+  carve_roots(c, b.one);
+  take_results(c, b.n, b.W, &b.roots, &b.flags);
+}
+static void carve_batch_stage(Carver& c, BatchBufs& b) {  // the page-locked stage
+  carve_stage(c, b.one);
+  b.hidx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
+  take_mask_list(c, b.n, b.W, &b.hmask, &b.hlist0);
+  take_results(c, b.n, b.W, &b.hroots, &b.hflags);
+}
+template <class B>
+static size_t carved(void (*walk)(Carver&, B&), void* base, B& b) {
   Carver c(base);
   walk(c, b);
   return c.size();
 }
+// The scratch slots of either form, with their walks: what is allocated, and what
+// cel_dev_repair_batch_scratch_size adds up.
+template <class B>
+struct SlotWalk {
+  int slot;
+  void (*walk)(Carver&, B&);
+};
+constexpr SlotWalk<RepairBufs> kSquareSlots[] = {
+    {S_IN, carve_in}, {S_AUX, carve_aux}, {S_MASK, carve_mask}, {S_WORK, carve_work}, {S_ROOTS, carve_roots}};
+constexpr SlotWalk<BatchBufs> kBatchSlots[] = {{S_IN, carve_batch_in},     {S_AUX, carve_batch_aux},     {S_MASK, carve_batch_mask},
+                                               {S_WORK, carve_batch_work}, {S_ROOTS, carve_batch_roots}};
+template <class B, size_t N>
+static size_t slots_size(const SlotWalk<B> (&slots)[N], B& b) {
+  size_t total = 0;
+  for (const auto& s : slots) total += carved(s.walk, nullptr, b);
+  return total;
+}
 
-// `list` into the next axis-list slot, uploaded on stream s. Every slot in flight: drain
-// both streams (the side stream's compares read the lists too), then reuse.
-static cel_status upload_list(cel_ctx* ctx, RepairBufs& b, const std::vector<int32_t>& list, hipStream_t s,
+// b's scratch slots and page-locked stage (W and n set), the ctx's streams and the repair's
+// own events: everything of PassBufs but eds.
+template <class B, size_t N>
+static cel_status carve_bufs(cel_ctx* ctx, const SlotWalk<B> (&slots)[N], void (*stage)(Carver&, B&), B* b) {
+  hipError_t e = hipSuccess;
+  for (const auto& s : slots) {
+    void* p = scratch(ctx, s.slot, carved(s.walk, nullptr, *b), &e);
+    if (!p) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+    carved(s.walk, p, *b);
+  }
+  b->res_bytes = (size_t)(reinterpret_cast<uint8_t*>(b->flags) - b->roots) + (size_t)b->n * 2 * b->W * 4;  // roots .. last flag
+  if (!host_stage(ctx, carved(stage, nullptr, *b))) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
+  carved(stage, ctx->hstage, *b);
+  b->slot = 0;
+  // the side stream is the batch pipeline's (the ctx lock is held); the events are the repair's own
+  b->main = ctx->stream;
+  b->side = ctx->sub[0];
+  b->ev_main = ctx->ev_repair_main;
+  b->ev_done = ctx->ev_repair_done;
+  return CEL_OK;
+}
+
+// `list` into the next list slot, uploaded on stream s. Every slot in flight: drain both
+// streams (the side stream's compares read the lists too), then reuse.
+static cel_status upload_list(cel_ctx* ctx, PassBufs& b, const std::vector<int32_t>& list, hipStream_t s,
                               int32_t** d_list) {
   hipError_t e;
   if (b.slot == kIdxSlots) {
@@ -122,8 +199,8 @@ static cel_status upload_list(cel_ctx* ctx, RepairBufs& b, const std::vector<int
       return hip_fail(ctx, e, "sync");
     b.slot = 0;
   }
-  int32_t* hidx = b.hidx + (size_t)b.slot * b.W;
-  *d_list = b.idx + (size_t)b.slot * b.W;
+  int32_t* hidx = b.hidx + (size_t)b.slot * b.slot_len();
+  *d_list = b.idx + (size_t)b.slot * b.slot_len();
   b.slot++;
   std::memcpy(hidx, list.data(), list.size() * 4);
   if ((e = hipMemcpyAsync(*d_list, hidx, list.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
@@ -214,73 +291,207 @@ static hipError_t decode_axes(cel_ctx* ctx, RepairBufs& b, uint32_t k, const int
   return launch_scatter_axes(b.eds, b.mask, W, idx, is_col, na, dense, s);
 }
 
-// rsmt2d solveCrossword's decode of `list` (incomplete axes of one direction), in two
-// halves so the host can put other side-stream work between them:
-//   solve_issue  the decode on the main stream (in place in the square, or gather ->
-//                decode -> scatter), then ev_main;
-//   solve_check  the encoding check of the solved axes on the side stream, after ev_main.
-// Nothing is synchronised: every flag is read back once at the end of the repair.
+// A pass's decode as issued: what its encoding check, enqueued later, needs.
 struct Issued {
   uint32_t na = 0;
-  uint32_t d = 0;
+  int is_col = 0;
+  uint32_t d = 0;  // dense path: which dense buffer
   int32_t* idx = nullptr;
 };
 
-static cel_status solve_issue(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_col, const std::vector<int32_t>& list,
-                              Issued* out, int32_t* uploaded = nullptr) {
-  const Range range("repair.solve");
-  const uint32_t W = 2 * k, na = (uint32_t)list.size();
-  out->na = na;
-  if (!na) return CEL_OK;
-  const uint32_t d = out->d = b.solves++ & 1u;
+// The names of the schedule's ranges in a trace.
+struct RangeNames {
+  const char *solve, *check, *plan, *fill;
+};
+
+// What differs on the device between the schedule of one square and of a merged batch: the
+// decode of a pass (main stream), the encoding check of the axes it solved and of complete
+// axes (side stream). run_passes enqueues everything around them.
+//
+// One square, any k. W = 32 .. 256 decode and check in the square; else the decode is gather ->
+// decode -> scatter through dense[d], d alternating, and its check reads dense[d]: the decode
+// waits for ev_side[d] (the side stream is done with the buffer), the check records it. That
+// check must be enqueued before the solve after next, which reuses dense[d].
+struct SquareOps {
+  static constexpr RangeNames kRanges = {"repair.solve", "repair.check", "repair.plan", "repair.fill"};
+  cel_ctx* ctx;
+  RepairBufs& b;
+  const uint32_t k = b.W / 2;
+  const bool in_square = rs_decode_axis_supported(b.W, kShare);
+  hipError_t decode(Issued& s) {
+    s.d = b.solves++ & 1u;
+    hipError_t e;
+    if (!in_square && (e = hipStreamWaitEvent(b.main, b.ev_side[s.d], 0)) != hipSuccess) return e;
+    return decode_axes(ctx, b, k, s.idx, s.is_col, s.na, b.dense[s.d], b.main);
+  }
+  cel_status check_solved(const Issued& s) {
+    if (in_square) return check_complete(s.is_col, s.na, s.idx);  // the completed axes are checked in the square
+    const cel_status st = encode_check(ctx, b, k, s.is_col, s.na, b.dense[s.d], s.idx, b.side);
+    if (st != CEL_OK) return st;
+    const hipError_t e = hipEventRecord(b.ev_side[s.d], b.side);
+    return e == hipSuccess ? CEL_OK : hip_fail(ctx, e, "event");
+  }
+  cel_status check_complete(int is_col, uint32_t na, const int32_t* idx) {
+    return check_in_square(ctx, b, k, is_col, na, idx, b.side);
+  }
+};
+
+// The merged batch, k = 32, 64, 128: one launch serves every square with entries in the list
+// (square and direction are in the entry).
+struct BatchOps {
+  static constexpr RangeNames kRanges = {"repair.batch.solve", "repair.batch.check", "repair.batch.plan",
+                                         "repair.batch.fill"};
+  cel_ctx* ctx;
+  BatchBufs& b;
+  hipError_t decode(Issued& s) {
+    return launch_rs_decode_in_squares(b.eds, b.mask, b.W, b.n, s.idx, s.na, ctx->tables.mul8, b.main);
+  }
+  cel_status check_solved(const Issued& s) { return check_complete(s.is_col, s.na, s.idx); }
+  cel_status check_complete(int, uint32_t na, const int32_t* idx) {
+    const hipError_t e = launch_rs_check_axes_batch(b.eds, b.W / 2, b.n, idx, na, b.flags, b.side);
+    return e == hipSuccess ? CEL_OK : hip_fail(ctx, e, "encoding check");
+  }
+};
+
+// rsmt2d solveCrossword's decode of `list` (incomplete axes of one direction), in two
+// halves so the host can put other side-stream work between them:
+//   solve_issue  the decode on the main stream, then ev_main; `uploaded`: the list is on the
+//                device there already (the first pass, in the masks' upload);
+//   solve_check  the encoding check of the solved axes on the side stream, after ev_main
+//                (that solve's record or a later one of the main stream: the axes it checks
+//                are final from their pass on).
+// Nothing is synchronised: every flag is read back once at the end of the repair.
+template <class Ops>
+static cel_status solve_issue(Ops& ops, int is_col, const std::vector<int32_t>& list, Issued* out,
+                              int32_t* uploaded = nullptr) {
+  const Range range(Ops::kRanges.solve);
+  PassBufs& b = ops.b;
+  out->is_col = is_col;
+  out->na = (uint32_t)list.size();
+  if (!out->na) return CEL_OK;
   cel_status st;
-  if (uploaded) out->idx = uploaded;  // `list` is already on the device there
-  else if ((st = upload_list(ctx, b, list, b.main, &out->idx)) != CEL_OK) return st;
-  if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
-  hipError_t e = hipSuccess;
-  // dense path: the side stream is done with dense[d]
-  if (!rs_decode_axis_supported(W, kShare)) e = hipStreamWaitEvent(b.main, b.ev_side[d], 0);
-  if (e != hipSuccess || (e = decode_axes(ctx, b, k, out->idx, is_col, na, b.dense[d], b.main)) != hipSuccess ||
-      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
-    return hip_fail(ctx, e, "solve");
+  if (uploaded) out->idx = uploaded;
+  else if ((st = upload_list(ops.ctx, b, list, b.main, &out->idx)) != CEL_OK) return st;
+  if ((st = fuzz(ops.ctx, b.main)) != CEL_OK) return st;
+  hipError_t e;
+  if ((e = ops.decode(*out)) != hipSuccess || (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
+    return hip_fail(ops.ctx, e, "solve");
   return CEL_OK;
 }
 
-// The side half of a solve_issue, enqueued after it with ev_main that solve's record or a
-// later one of the main stream (the axes it checks are final from their pass on). Dense
-// path: it must be enqueued before the solve after next, which reuses dense[s.d] once
-// this check has recorded ev_side[s.d].
-static cel_status solve_check(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_col, const Issued& s) {
+template <class Ops>
+static cel_status solve_check(Ops& ops, const Issued& s) {
   if (!s.na) return CEL_OK;
-  const uint32_t W = 2 * k;
+  PassBufs& b = ops.b;
   hipError_t e;
-  if ((e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess) return hip_fail(ctx, e, "event");
-  cel_status st;
-  if ((st = fuzz(ctx, b.side)) != CEL_OK) return st;
-  if (rs_decode_axis_supported(W, kShare))  // the completed axes are checked in the square
-    return check_in_square(ctx, b, k, is_col, s.na, s.idx, b.side);
-  if ((st = encode_check(ctx, b, k, is_col, s.na, b.dense[s.d], s.idx, b.side)) != CEL_OK) return st;
-  if ((e = hipEventRecord(b.ev_side[s.d], b.side)) != hipSuccess) return hip_fail(ctx, e, "event");
-  return CEL_OK;
+  if ((e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess) return hip_fail(ops.ctx, e, "event");
+  const cel_status st = fuzz(ops.ctx, b.side);
+  return st != CEL_OK ? st : ops.check_solved(s);
 }
 
 // Encoding check of complete axes (preRepairSanityCheck, and the orthogonal axes a solve
 // completed) on the side stream. wait_main: after the main stream's latest work; without
 // it the caller guarantees the axes are final in the side stream's order already (the
 // orthogonal axes of a pass whose solve_check the side stream has passed).
-static cel_status check_pass(cel_ctx* ctx, RepairBufs& b, uint32_t k, int is_col, const std::vector<int32_t>& list,
-                             bool wait_main) {
-  const Range range("repair.check");
-  const uint32_t na = (uint32_t)list.size();
-  if (!na) return CEL_OK;
+template <class Ops>
+static cel_status check_pass(Ops& ops, int is_col, const std::vector<int32_t>& list, bool wait_main) {
+  const Range range(Ops::kRanges.check);
+  if (list.empty()) return CEL_OK;
+  PassBufs& b = ops.b;
   hipError_t e;
   if (wait_main &&
       ((e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess))
-    return hip_fail(ctx, e, "event");
+    return hip_fail(ops.ctx, e, "event");
   int32_t* idx;
   cel_status st;
-  if ((st = upload_list(ctx, b, list, b.side, &idx)) != CEL_OK || (st = fuzz(ctx, b.side)) != CEL_OK) return st;
-  return check_in_square(ctx, b, k, is_col, na, idx, b.side);
+  if ((st = upload_list(ops.ctx, b, list, b.side, &idx)) != CEL_OK || (st = fuzz(ops.ctx, b.side)) != CEL_OK) return st;
+  return ops.check_complete(is_col, (uint32_t)list.size(), idx);
+}
+
+// The pipelined pass schedule of a repair, of one square (SquarePasses, SquareOps) or of a
+// merged batch (BatchPasses, BatchOps), over the squares resident at b.eds with the host masks
+// hm. `first`: the first row pass by the plan's byte scan. No pass waits for the device; one
+// sync at the end, after which b.hroots holds every root of the final squares and b.hflags
+// every encoding-check flag, and both streams are idle. plan: built here from plan_args, left
+// for the verdicts.
+//
+// Streams and events. The solve chain (upload of a pass's list, its decode) is the main
+// stream's; every encoding check is the side stream's, and its outcome is only read at the
+// end, so no check is on the chain's critical path.
+// - The masks go up with the first row pass's list riding behind them, and that pass's decode
+//   is enqueued before the host builds any bookkeeping (the mask bitsets, the sanity lists),
+//   which then runs beside it. The flags are the side stream's (its checks): zeroed there,
+//   after ev_main says the masks are up.
+// - The sanity checks come next, each after a fresh ev_main (everything the main stream has
+//   been given so far); the axes they read are complete from the start and never change.
+// - Each pass's encoding check is enqueued after the next pass's decode, so the host's
+//   enqueue of it is off the chain. It waits for ev_main as last recorded, the next decode's:
+//   later than it needs, and right, since the axes it checks are final from their own pass on.
+// - A pass's orthogonal checks follow that pass's own check on the side stream, which has
+//   then passed the ev_main that completed them: they wait for nothing more. They are held
+//   back (`pending`) until the next decode is enqueued, for the same reason.
+// - The last pass's checks go to the side stream ahead of the commit's dozen launches, so they
+//   run beside its leaf hashing instead of trailing its tree levels. The main stream then
+//   waits for ev_done, the side stream's last check, before the one download of roots and flags.
+// - An early return drains the side stream: no check is left running on the ctx's scratch.
+template <class Plan, class Ops, class... PlanArgs>
+static cel_status run_passes(Ops& ops, const std::vector<uint8_t>& hm, const std::vector<int32_t>& first,
+                             std::unique_ptr<Plan>& plan, const PlanArgs&... plan_args) {
+  cel_ctx* ctx = ops.ctx;
+  PassBufs& b = ops.b;
+  const uint32_t W = b.W, n = b.n;
+  hipError_t e = hipSuccess;
+  cel_status st;
+  struct SideDrain {
+    hipStream_t side;
+    ~SideDrain() { (void)hipStreamSynchronize(side); }
+  } drain{b.side};
+  std::memcpy(b.hmask, hm.data(), hm.size());
+  if (!first.empty()) std::memcpy(b.hlist0, first.data(), first.size() * 4);
+  const size_t up_b = (size_t)(reinterpret_cast<uint8_t*>(b.hlist0) - b.hmask) + first.size() * 4;
+  if ((e = hipMemcpyAsync(b.mask, b.hmask, up_b, hipMemcpyHostToDevice, b.main)) != hipSuccess ||
+      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess ||
+      (e = hipMemsetAsync(b.flags, 0, (size_t)n * 2 * W * 4, b.side)) != hipSuccess)
+    return hip_fail(ctx, e, "H2D");
+  Issued prev;
+  if ((st = solve_issue(ops, 0, first, &prev, b.list0)) != CEL_OK) return st;
+  bool first_issued = !first.empty();
+  {
+    const Range plan_range(Ops::kRanges.plan);
+    plan.reset(new Plan(plan_args...));
+    for (int is_col = 0; is_col < 2; is_col++)
+      if ((st = check_pass(ops, is_col, plan->sanity[is_col], true)) != CEL_OK) return st;
+  }
+  // the checks of the pass `prev`: its own, then the orthogonal axes it completed
+  std::vector<int32_t> list, pending;
+  auto checks = [&] {
+    const cel_status sc = solve_check(ops, prev);
+    return sc != CEL_OK ? sc : check_pass(ops, !prev.is_col, pending, false);
+  };
+  int is_col;
+  while (plan->next(&is_col, list)) {
+    if (first_issued) {  // the first row pass (the same list, issued above)
+      first_issued = false;
+    } else {
+      Issued s1;
+      if ((st = solve_issue(ops, is_col, list, &s1)) != CEL_OK || (st = checks()) != CEL_OK) return st;
+      prev = s1;
+    }
+    // sequential view of the pass: each solve fills its missing cells, completing the
+    // orthogonal axes whose last missing cell it held
+    const Range fill_range(Ops::kRanges.fill);
+    plan->apply(pending);
+  }
+  if ((st = fuzz(ctx, b.main)) != CEL_OK || (st = checks()) != CEL_OK) return st;
+  if ((e = launch_commit(b.eds, W / 2, n, b.roots, b.roots + (size_t)n * W * kNode, nullptr, nullptr, b.work, false,
+                         b.main)) != hipSuccess)
+    return hip_fail(ctx, e, "roots");
+  if ((e = hipEventRecord(b.ev_done, b.side)) != hipSuccess || (e = hipStreamWaitEvent(b.main, b.ev_done, 0)) != hipSuccess)
+    return hip_fail(ctx, e, "join");
+  if ((e = hipMemcpyAsync(b.hroots, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
+    return hip_fail(ctx, e, "D2H");
+  if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
+  return CEL_OK;
 }
 
 struct RepairOut {
@@ -321,30 +532,6 @@ static cel_status fail_axis(cel_ctx* ctx, const RepairBufs& b, const std::vector
                              : std::string("byzantine ") + (is_col ? "column" : "row") + " " + std::to_string(idx));
 }
 
-// Commit every root of the square on the main stream beside the side stream's last checks,
-// join the streams and read roots and flags back (one page-locked copy: b.hroots, b.hflags).
-static cel_status verify_square(cel_ctx* ctx, RepairBufs& b, uint32_t k, int last_col, const Issued& last,
-                                int pending_col, const std::vector<int32_t>& pending) {
-  const size_t roots_b = (size_t)b.W * kNode;
-  hipError_t e;
-  cel_status st;
-  if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
-  // the last pass's checks go to the side stream ahead of the commit's dozen launches, so
-  // they run beside its leaf hashing instead of trailing its tree levels
-  if ((st = solve_check(ctx, b, k, last_col, last)) != CEL_OK ||
-      (st = check_pass(ctx, b, k, pending_col, pending, false)) != CEL_OK)
-    return st;
-  if ((e = launch_commit(b.eds, k, 1, b.roots, b.roots + roots_b, nullptr, nullptr, b.work, false, b.main)) !=
-      hipSuccess)
-    return hip_fail(ctx, e, "roots");
-  if ((e = hipEventRecord(b.ev_done, b.side)) != hipSuccess || (e = hipStreamWaitEvent(b.main, b.ev_done, 0)) != hipSuccess)
-    return hip_fail(ctx, e, "join");
-  if ((e = hipMemcpyAsync(b.hroots, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
-    return hip_fail(ctx, e, "D2H");
-  if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
-  return CEL_OK;
-}
-
 // rsmt2d's own solve order, for a square the pass-parallel schedule found byzantine.
 //
 // solveCrossword sweeps `for i { solveCrosswordRow(i); solveCrosswordCol(i) }`, and on
@@ -377,7 +564,7 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
   std::vector<int32_t> h_flags((size_t)2 * W);
   hipError_t e;
   cel_status st;
-  // both streams are idle (verify_square synchronised the joined streams); the square keeps
+  // both streams are idle (run_passes synchronised the joined streams); the square keeps
   // the bytes of every cell known at the start (decoders store erased cells only)
   std::memcpy(b.hmask, hm.data(), cells);
   if ((e = hipMemcpyAsync(b.mask, b.hmask, cells, hipMemcpyHostToDevice, b.main)) != hipSuccess ||
@@ -474,160 +661,72 @@ static cel_status repair_exact(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>
   return CEL_OK;
 }
 
-// rsmt2d Repair over the EDS resident at b.eds. hm = host presence mask (updated: all
-// ones on success, the mask before the failing solve on a byzantine / bad-root error,
-// the mask after the last solve when stuck). No pass waits for the device. Root checks
-// are deferred: an axis, once complete, never changes, so one commit pass over the final
-// square gives every root rsmt2d checks on the way, and the checks are replayed in
-// rsmt2d's order, reporting the first failure.
+static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs* b) {
+  hipError_t e = hipSuccess;
+  b->W = 2 * k;
+  if (own_eds) b->eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, (size_t)b->W * b->W * kShare, &e));
+  if (!b->eds) return fail(ctx, CEL_ENOMEM, "device allocation failed");
+  const cel_status st = carve_bufs(ctx, kSquareSlots, carve_stage, b);
+  if (st != CEL_OK) return st;
+  b->solves = 0;
+  b->ev_side[0] = ctx->ev_repair_side[0];
+  b->ev_side[1] = ctx->ev_repair_side[1];
+  // no stale record of an earlier call may gate this one: both streams start from here
+  if ((e = hipEventRecord(b->ev_side[0], b->side)) != hipSuccess || (e = hipEventRecord(b->ev_side[1], b->side)) != hipSuccess)
+    return hip_fail(ctx, e, "event");
+  return CEL_OK;
+}
+
+// A status a repair ends with for its square, against an error of the call.
+static bool is_outcome(cel_status st) {
+  return st == CEL_OK || st == CEL_EBYZANTINE || st == CEL_EBADROOT || st == CEL_EUNREPAIRABLE;
+}
+
+// One square's verdict after run_passes: its checks replayed in rsmt2d's order (sq.order) over
+// its roots (`got`, [2][W] by direction and axis) and flags, the first failure reported. hm:
+// the square's host mask, updated: all ones on success, the mask before the failing solve on
+// a byzantine / bad-root error, the mask after the last solve when stuck. Root checks are
+// deferred: an axis, once complete, never changes, so the commit over the final square gives
+// every root rsmt2d checks on the way.
 //
-// The solves run in passes (every solvable row, then every solvable column, ...), which
+// The solves ran in passes (every solvable row, then every solvable column, ...), which
 // decodes whole directions at once. When every check passes, the outcome equals that of
 // rsmt2d's sweep order (row i, then column i): all cells of the final square then agree
 // with valid codewords whose roots match, so any order decodes the same bytes and passes
 // the same checks, and the set of axes that can be solved is the same closure. Only a
 // failing solve or orthogonal check depends on the order; that square is replayed in
-// rsmt2d's order by repair_exact.
-static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>& hm, uint32_t k,
-                              const uint8_t* row_roots, const uint8_t* col_roots, const RepairOut& out) {
-  const uint32_t W = 2 * k;
-  const size_t cells = (size_t)W * W;
-  hipStream_t s = b.main;
-  hipError_t e = hipSuccess;
-  cel_status st;
-  // an early return leaves no side-stream work running on the ctx's scratch buffers
-  struct SideDrain {
-    hipStream_t side;
-    ~SideDrain() { (void)hipStreamSynchronize(side); }
-  } drain{b.side};
-  // The first row pass goes to the device before the host builds its bookkeeping (the
-  // mask bitsets, the sanity lists), which then runs beside the decode; its axis list
-  // rides in the mask's upload.
-  std::vector<int32_t> list, orth;
-  const std::vector<int32_t> first = first_row_pass(hm, k);
-  std::memcpy(b.hmask, hm.data(), cells);
-  if (!first.empty()) std::memcpy(b.hlist0, first.data(), first.size() * 4);
-  const size_t up_b = (size_t)(reinterpret_cast<uint8_t*>(b.hlist0) - b.hmask) + first.size() * 4;
-  // the flags are the side stream's (its checks), zeroed there after the mask is up
-  if ((e = hipMemcpyAsync(b.mask, b.hmask, up_b, hipMemcpyHostToDevice, s)) != hipSuccess ||
-      (e = hipEventRecord(b.ev_main, s)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess ||
-      (e = hipMemsetAsync(b.flags, 0, 2 * (size_t)W * 4, b.side)) != hipSuccess)
-    return hip_fail(ctx, e, "H2D");
-  // Each pass's encoding check (side stream) is enqueued after the next pass's decode, so
-  // the host's enqueue of it is off the solve chain (the checked axes are final from their
-  // pass on; the dense path's buffer dense[d] is reused two passes later, after the check
-  // has recorded ev_side[d]).
-  Issued prev;
-  int prev_col = 0;
-  if ((st = solve_issue(ctx, b, k, 0, first, &prev, b.list0)) != CEL_OK) return st;
-  bool first_issued = !first.empty();
-  std::unique_ptr<Range> plan_range(new Range("repair.plan"));
-  MaskBits mb(hm, W);
-  std::vector<Check> order;
-  std::vector<Solve> solves;
-  // preRepairSanityCheck: for i: row i, column i
-  {
-    std::vector<int32_t> comp[2];
-    for (uint32_t i = 0; i < W; i++)
-      for (int is_col = 0; is_col < 2; is_col++)
-        if (mb.cnt[is_col][i] == W) {
-          order.push_back({Check::SANITY, is_col, (int32_t)i, -1});
-          comp[is_col].push_back((int32_t)i);
-        }
-    for (int is_col = 0; is_col < 2; is_col++)
-      if ((st = check_pass(ctx, b, k, is_col, comp[is_col], true)) != CEL_OK) return st;
-  }
-  // The orthogonal checks of a pass are issued after the next pass's decode (or the final
-  // commit), so the host's enqueue of them is not on the solve chain; the side stream runs
-  // them right after that pass's own encoding checks.
-  std::vector<int32_t> pending;
-  int pending_col = 0;
-  plan_range.reset();
-  // passes: all solvable rows, then all solvable columns, until solved or stuck
-  bool solved = false;
-  std::vector<std::vector<int32_t>> by_solve;
-  for (;;) {
-    bool progress = false;
-    for (int is_col = 0; is_col < 2; is_col++) {
-      list.clear();
-      for (uint32_t i = 0; i < W; i++)
-        if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) list.push_back((int32_t)i);
-      if (list.empty()) continue;
-      if (first_issued) {  // the first row pass (the same list, issued above)
-        first_issued = false;
-      } else {
-        Issued s1;
-        if ((st = solve_issue(ctx, b, k, is_col, list, &s1)) != CEL_OK ||
-            (st = solve_check(ctx, b, k, prev_col, prev)) != CEL_OK ||
-            (st = check_pass(ctx, b, k, pending_col, pending, false)) != CEL_OK)
-          return st;
-        prev = s1;
-        prev_col = is_col;
-        pending.clear();
-      }
-      // sequential view of the pass: solve i fills its missing cells, completing the
-      // orthogonal axes whose last missing cell it held
-      const Range fill_range("repair.fill");
-      mb.fill_pass(is_col, list, by_solve);
-      log_pass(is_col, list, by_solve, order, solves, orth);
-      // pending is empty here: the previous pass's orthogonal checks were issued (and
-      // cleared) right after this pass's solve above, or this is the first pass
-      pending.swap(orth);
-      pending_col = !is_col;
-      progress = true;
-    }
-    if (mb.total == cells) {
-      solved = true;
-      break;
-    }
-    if (!progress) break;
-  }
-  if ((st = verify_square(ctx, b, k, prev_col, prev, pending_col, pending)) != CEL_OK) return st;
+// rsmt2d's order by repair_exact, through b (b.eds: the square).
+static cel_status verdict(cel_ctx* ctx, RepairBufs& b, const SquarePasses& sq, const uint8_t* got, const int32_t* flags,
+                          const uint8_t* row_roots, const uint8_t* col_roots, std::vector<uint8_t>& hm,
+                          const RepairOut& out) {
   const uint8_t* const exp[2] = {row_roots, col_roots};
   cel_status code;
-  const long f = first_failure(order.data(), order.size(), {b.hroots, kNode, RootRecords::BY_AXIS}, exp, b.hflags, W, &code);
+  const long f = first_failure(sq.order.data(), sq.order.size(), {got, kNode, RootRecords::BY_AXIS}, exp, flags, sq.W, &code);
   if (f >= 0) {
-    const Check& c = order[(size_t)f];
+    const Check& c = sq.order[(size_t)f];
     if (c.kind == Check::SANITY) return fail_axis(ctx, b, hm, out, code, c.is_col, c.idx, false);
-    return repair_exact(ctx, b, hm, k, row_roots, col_roots, out);
+    // a batch's single-square prefix has its pointers, not yet its streams and events
+    cel_status st;
+    if (!b.main && (st = repair_bufs(ctx, sq.k, false, &b)) != CEL_OK) return st;
+    return repair_exact(ctx, b, hm, sq.k, row_roots, col_roots, out);
   }
-  if (!solved) {
-    rollback(hm, W, solves, solves.size());
+  if (!sq.solved()) {
+    rollback(hm, sq.W, sq.solves, sq.solves.size());
     return fail(ctx, CEL_EUNREPAIRABLE, "failed to solve data square");
   }
   std::fill(hm.begin(), hm.end(), (uint8_t)1);
   return CEL_OK;
 }
 
-static cel_status repair_bufs(cel_ctx* ctx, uint32_t k, bool own_eds, RepairBufs* b) {
-  hipError_t e = hipSuccess;
-  b->W = 2 * k;
-  if (own_eds) b->eds = static_cast<uint8_t*>(scratch(ctx, S_EDS, (size_t)b->W * b->W * kShare, &e));
-  if (!b->eds) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  auto slot = [&](int sl, void (*walk)(Carver&, RepairBufs&)) {
-    void* p = scratch(ctx, sl, carved(walk, nullptr, *b), &e);
-    if (p) carved(walk, p, *b);
-    return p != nullptr;
-  };
-  if (!slot(S_IN, carve_in) || !slot(S_AUX, carve_aux) || !slot(S_MASK, carve_mask) || !slot(S_WORK, carve_work) ||
-      !slot(S_ROOTS, carve_roots))
-    return fail(ctx, CEL_ENOMEM, "device allocation failed");
-  b->res_bytes = (size_t)(reinterpret_cast<uint8_t*>(b->flags) - b->roots) + 2 * (size_t)b->W * 4;  // roots .. last flag
-  if (!host_stage(ctx, carved(carve_stage, nullptr, *b))) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  carved(carve_stage, ctx->hstage, *b);
-  b->slot = 0;
-  b->solves = 0;
-  // the side stream is the batch pipeline's (the ctx lock is held); the events are the repair's own
-  b->main = ctx->stream;
-  b->side = ctx->sub[0];
-  b->ev_main = ctx->ev_repair_main;
-  b->ev_side[0] = ctx->ev_repair_side[0];
-  b->ev_side[1] = ctx->ev_repair_side[1];
-  b->ev_done = ctx->ev_repair_done;
-  // no stale record of an earlier call may gate this one: both streams start from here
-  if ((e = hipEventRecord(b->ev_side[0], b->side)) != hipSuccess || (e = hipEventRecord(b->ev_side[1], b->side)) != hipSuccess)
-    return hip_fail(ctx, e, "event");
-  return CEL_OK;
+// rsmt2d Repair over the EDS resident at b.eds, hm = host presence mask (updated as verdict
+// leaves it): the plan's first pass, the pass schedule, the verdict.
+static cel_status repair_core(cel_ctx* ctx, RepairBufs& b, std::vector<uint8_t>& hm, uint32_t k,
+                              const uint8_t* row_roots, const uint8_t* col_roots, const RepairOut& out) {
+  SquareOps ops{ctx, b};
+  std::unique_ptr<SquarePasses> plan;
+  const cel_status st = run_passes(ops, hm, first_row_pass(hm, k), plan, hm.data(), k);
+  if (st != CEL_OK) return st;
+  return verdict(ctx, b, *plan, b.hroots, b.hflags, row_roots, col_roots, hm, out);
 }
 
 // Both entry points with ctx->mu held: the repair of the caller's device square d_eds, or,
@@ -652,7 +751,7 @@ static cel_status repair_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds, uint8
   if (!d_eds && (e = hipMemcpyAsync(b.eds, h_eds, eds_b, hipMemcpyHostToDevice, s)) != hipSuccess)
     return hip_fail(ctx, e, "H2D");
   st = repair_core(ctx, b, hm, k, row_roots, col_roots, out);
-  if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
+  if (!is_outcome(st)) return st;
   if (!d_eds) {  // the (partially) repaired square goes back either way, with the mask it is valid under
     if ((e = hipMemcpyAsync(h_eds, b.eds, eds_b, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(ctx, e, "D2H");
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(ctx, e, "sync");
@@ -663,168 +762,15 @@ static cel_status repair_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds, uint8
 
 // ------------------------------------------------------------ batch of squares
 //
-// cel_dev_repair_batch: the schedule of repair_core over n squares of one k (32, 64, 128: the
-// in-square kernels) at once. Every pass is the merged pass of repair_plan.hpp (BatchPasses):
-// one decode launch on the main stream and one check launch on the side stream serve every
-// square that has axes in it, one commit takes all n squares' roots, and one copy brings the
-// roots and flags back. Only the verdict is per square.
-//
-// Every scratch slot and the page-locked stage start with the single-square layout (the same
-// walk as RepairBufs), the batch's regions after it: a square whose SOLVE or ORTH check
-// fails is replayed alone by repair_exact through a RepairBufs whose eds is that square's
-// slice of the batch, without a reallocation under the batch's buffers.
-struct BatchBufs {
-  uint32_t W, n;
-  RepairBufs one;     // the single-square prefix of every slot (eds unset)
-  uint8_t* eds;       // [n][W][W][512]
-  uint8_t* mask;      // [n][W*W], then the first pass's entries (one upload for both)
-  int32_t* list0;     // [n*W]
-  uint8_t* work;      // the n-square commit's workspace
-  uint8_t* roots;     // [n][W][90] row roots, [n][W][90] column roots, then the flags
-  int32_t* flags;     // [n][2][W] by (square, direction, axis)
-  uint8_t* hroots;    // page-locked copy of roots + flags (one D2H of res_bytes)
-  int32_t* hflags;
-  size_t res_bytes;
-  int32_t* idx;       // [kIdxSlots][n*W] device entry lists
-  int32_t* hidx;      // page-locked staging of the same
-  uint8_t* hmask;     // page-locked staging of masks + first entries
-  int32_t* hlist0;
-  uint32_t slot;
-  hipStream_t main, side;
-  hipEvent_t ev_main, ev_done;
-  size_t slot_len() const { return (size_t)n * W; }
-};
-
-static void take_batch_mask_list(Carver& c, const BatchBufs& b, uint8_t** mask, int32_t** list0) {
-  *mask = c.take<uint8_t>((size_t)b.n * b.W * b.W);
-  *list0 = c.take<int32_t>(b.slot_len() * 4);
-}
-static void take_batch_results(Carver& c, const BatchBufs& b, uint8_t** roots, int32_t** flags) {
-  *roots = c.take<uint8_t>((size_t)b.n * 2 * b.W * kNode);
-  *flags = c.take<int32_t>((size_t)b.n * 2 * b.W * 4);
-}
-static void carve_batch_in(Carver& c, BatchBufs& b) { carve_in(c, b.one); }  // S_IN: the replay's alone
-static void carve_batch_aux(Carver& c, BatchBufs& b) {                       // S_AUX
-  carve_aux(c, b.one);
-  b.idx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
-}
-static void carve_batch_mask(Carver& c, BatchBufs& b) {  // S_MASK
-  carve_mask(c, b.one);
-  take_batch_mask_list(c, b, &b.mask, &b.list0);
-}
-static void carve_batch_work(Carver& c, BatchBufs& b) {  // S_WORK
-  carve_work(c, b.one);
-  b.work = c.take<uint8_t>(nmt_workspace_size(b.W / 2, b.n));
-}
-static void carve_batch_roots(Carver& c, BatchBufs& b) {  // S_ROOTS
-  carve_roots(c, b.one);
-  take_batch_results(c, b, &b.roots, &b.flags);
-}
-static void carve_batch_stage(Carver& c, BatchBufs& b) {  // the page-locked stage
-  carve_stage(c, b.one);
-  b.hidx = c.take<int32_t>((size_t)kIdxSlots * b.slot_len() * 4);
-  take_batch_mask_list(c, b, &b.hmask, &b.hlist0);
-  take_batch_results(c, b, &b.hroots, &b.hflags);
-}
-static size_t carved(void (*walk)(Carver&, BatchBufs&), void* base, BatchBufs& b) {
-  Carver c(base);
-  walk(c, b);
-  return c.size();
-}
-constexpr struct {
-  int slot;
-  void (*walk)(Carver&, BatchBufs&);
-} kBatchSlots[] = {{S_IN, carve_batch_in},     {S_AUX, carve_batch_aux},     {S_MASK, carve_batch_mask},
-                   {S_WORK, carve_batch_work}, {S_ROOTS, carve_batch_roots}};
+// cel_dev_repair_batch: the same schedule over n squares of one k (32, 64, 128: the in-square
+// kernels) at once. Every pass is the merged pass of repair_plan.hpp (BatchPasses): one decode
+// launch on the main stream and one check launch on the side stream serve every square that
+// has axes in it, one commit takes all n squares' roots, and one copy brings the roots and
+// flags back. Only the verdict is per square.
 
 // k = 32, 64, 128 and more than one square: the merged schedule; else square after square.
 static bool batch_merged(uint32_t k, uint32_t n) {
   return n > 1 && (k == 32 || k == 64 || k == 128) && entries_fit(n, 2 * k);
-}
-
-static cel_status batch_bufs(cel_ctx* ctx, uint32_t k, uint32_t n, BatchBufs* b) {
-  hipError_t e = hipSuccess;
-  b->W = b->one.W = 2 * k;
-  b->n = n;
-  for (const auto& s : kBatchSlots) {
-    void* p = scratch(ctx, s.slot, carved(s.walk, nullptr, *b), &e);
-    if (!p) return fail(ctx, CEL_ENOMEM, "device allocation failed");
-    carved(s.walk, p, *b);
-  }
-  b->res_bytes = (size_t)(reinterpret_cast<uint8_t*>(b->flags) - b->roots) + (size_t)n * 2 * b->W * 4;
-  if (!host_stage(ctx, carved(carve_batch_stage, nullptr, *b))) return fail(ctx, CEL_ENOMEM, "page-locked allocation failed");
-  carved(carve_batch_stage, ctx->hstage, *b);
-  b->slot = 0;
-  b->main = ctx->stream;
-  b->side = ctx->sub[0];
-  b->ev_main = ctx->ev_repair_main;
-  b->ev_done = ctx->ev_repair_done;
-  return CEL_OK;
-}
-
-// `list` into the next entry-list slot, uploaded on stream s (upload_list's rule).
-static cel_status upload_entries(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, hipStream_t s,
-                                 int32_t** d_list) {
-  hipError_t e;
-  if (b.slot == kIdxSlots) {
-    if ((e = hipStreamSynchronize(b.main)) != hipSuccess || (e = hipStreamSynchronize(b.side)) != hipSuccess)
-      return hip_fail(ctx, e, "sync");
-    b.slot = 0;
-  }
-  int32_t* hidx = b.hidx + (size_t)b.slot * b.slot_len();
-  *d_list = b.idx + (size_t)b.slot * b.slot_len();
-  b.slot++;
-  std::memcpy(hidx, list.data(), list.size() * 4);
-  if ((e = hipMemcpyAsync(*d_list, hidx, list.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-    return hip_fail(ctx, e, "H2D");
-  return CEL_OK;
-}
-
-// A merged pass's decode on the main stream, then ev_main (solve_issue); `uploaded`: the
-// entries are on the device already (the first pass, in the masks' upload).
-static cel_status batch_solve_issue(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, Issued* out,
-                                    int32_t* uploaded = nullptr) {
-  const Range range("repair.batch.solve");
-  out->na = (uint32_t)list.size();
-  if (!out->na) return CEL_OK;
-  cel_status st;
-  if (uploaded) out->idx = uploaded;
-  else if ((st = upload_entries(ctx, b, list, b.main, &out->idx)) != CEL_OK) return st;
-  if ((st = fuzz(ctx, b.main)) != CEL_OK) return st;
-  hipError_t e;
-  if ((e = launch_rs_decode_in_squares(b.eds, b.mask, b.W, b.n, out->idx, out->na, ctx->tables.mul8, b.main)) !=
-          hipSuccess ||
-      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess)
-    return hip_fail(ctx, e, "solve");
-  return CEL_OK;
-}
-
-// Its encoding check on the side stream, after ev_main (solve_check).
-static cel_status batch_solve_check(cel_ctx* ctx, BatchBufs& b, const Issued& s) {
-  if (!s.na) return CEL_OK;
-  hipError_t e;
-  if ((e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess) return hip_fail(ctx, e, "event");
-  cel_status st;
-  if ((st = fuzz(ctx, b.side)) != CEL_OK) return st;
-  if ((e = launch_rs_check_axes_batch(b.eds, b.W / 2, b.n, s.idx, s.na, b.flags, b.side)) != hipSuccess)
-    return hip_fail(ctx, e, "encoding check");
-  return CEL_OK;
-}
-
-// Encoding check of complete axes (sanity, orthogonal completions) on the side stream (check_pass).
-static cel_status batch_check_pass(cel_ctx* ctx, BatchBufs& b, const std::vector<int32_t>& list, bool wait_main) {
-  const Range range("repair.batch.check");
-  if (list.empty()) return CEL_OK;
-  hipError_t e;
-  if (wait_main &&
-      ((e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess))
-    return hip_fail(ctx, e, "event");
-  int32_t* idx;
-  cel_status st;
-  if ((st = upload_entries(ctx, b, list, b.side, &idx)) != CEL_OK || (st = fuzz(ctx, b.side)) != CEL_OK) return st;
-  if ((e = launch_rs_check_axes_batch(b.eds, b.W / 2, b.n, idx, (uint32_t)list.size(), b.flags, b.side)) != hipSuccess)
-    return hip_fail(ctx, e, "encoding check");
-  return CEL_OK;
 }
 
 struct BatchOut {
@@ -838,6 +784,13 @@ struct BatchOut {
                      byz_shares ? byz_shares + (size_t)i * W * kShare : nullptr,
                      byz_present ? byz_present + (size_t)i * W : nullptr};
   }
+  // Square i ended with st. false: st is an error of the call, not a square's outcome.
+  bool record(cel_ctx* ctx, uint32_t i, cel_status st, std::string* first_error) const {
+    if (!is_outcome(st)) return false;
+    if (st != CEL_OK && first_error->empty()) *first_error = "square " + std::to_string(i) + ": " + ctx->last_error;
+    status[i] = st;
+    return true;
+  }
 };
 
 // The squares resident at b.eds, masks hm ([n][W*W] bytes 0 / 1, updated per square as
@@ -846,93 +799,24 @@ static cel_status repair_batch_core(cel_ctx* ctx, BatchBufs& b, std::vector<uint
                                     const uint8_t* row_roots, const uint8_t* col_roots, const BatchOut& out,
                                     std::string* first_error) {
   const uint32_t W = 2 * k, n = b.n;
-  const size_t cells = (size_t)W * W;
-  hipError_t e = hipSuccess;
-  cel_status st;
-  struct SideDrain {
-    hipStream_t side;
-    ~SideDrain() { (void)hipStreamSynchronize(side); }
-  } drain{b.side};
-  // every square's first row pass goes to the device before any bookkeeping exists; its
-  // entries ride in the masks' upload
-  const std::vector<int32_t> first = first_row_pass_batch(hm, n, k);
-  std::memcpy(b.hmask, hm.data(), n * cells);
-  if (!first.empty()) std::memcpy(b.hlist0, first.data(), first.size() * 4);
-  const size_t up_b = (size_t)(reinterpret_cast<uint8_t*>(b.hlist0) - b.hmask) + first.size() * 4;
-  if ((e = hipMemcpyAsync(b.mask, b.hmask, up_b, hipMemcpyHostToDevice, b.main)) != hipSuccess ||
-      (e = hipEventRecord(b.ev_main, b.main)) != hipSuccess || (e = hipStreamWaitEvent(b.side, b.ev_main, 0)) != hipSuccess ||
-      (e = hipMemsetAsync(b.flags, 0, (size_t)n * 2 * W * 4, b.side)) != hipSuccess)
-    return hip_fail(ctx, e, "H2D");
-  Issued prev;
-  if ((st = batch_solve_issue(ctx, b, first, &prev, b.list0)) != CEL_OK) return st;
-  bool first_issued = !first.empty();
-  std::unique_ptr<Range> plan_range(new Range("repair.batch.plan"));
-  BatchPasses bp(hm, n, k);
-  for (int is_col = 0; is_col < 2; is_col++)
-    if ((st = batch_check_pass(ctx, b, bp.sanity[is_col], true)) != CEL_OK) return st;
-  plan_range.reset();
-  // each pass's checks (its own, then the orthogonal completions) follow the next pass's decode
-  std::vector<int32_t> list, pending;
-  int is_col;
-  while (bp.next(&is_col, list)) {
-    if (first_issued) {  // the first row pass (the same entries, issued above)
-      first_issued = false;
-    } else {
-      Issued s1;
-      if ((st = batch_solve_issue(ctx, b, list, &s1)) != CEL_OK || (st = batch_solve_check(ctx, b, prev)) != CEL_OK ||
-          (st = batch_check_pass(ctx, b, pending, false)) != CEL_OK)
-        return st;
-      prev = s1;
-    }
-    const Range fill_range("repair.batch.fill");
-    bp.apply(pending);
-  }
-  // the last pass's checks beside the commit of all n squares, the join, one download
-  const size_t roots_b = (size_t)n * W * kNode;
-  if ((st = fuzz(ctx, b.main)) != CEL_OK || (st = batch_solve_check(ctx, b, prev)) != CEL_OK ||
-      (st = batch_check_pass(ctx, b, pending, false)) != CEL_OK)
-    return st;
-  if ((e = launch_commit(b.eds, k, n, b.roots, b.roots + roots_b, nullptr, nullptr, b.work, false, b.main)) != hipSuccess)
-    return hip_fail(ctx, e, "roots");
-  if ((e = hipEventRecord(b.ev_done, b.side)) != hipSuccess || (e = hipStreamWaitEvent(b.main, b.ev_done, 0)) != hipSuccess)
-    return hip_fail(ctx, e, "join");
-  if ((e = hipMemcpyAsync(b.hroots, b.roots, b.res_bytes, hipMemcpyDeviceToHost, b.main)) != hipSuccess)
-    return hip_fail(ctx, e, "D2H");
-  if ((e = hipStreamSynchronize(b.main)) != hipSuccess) return hip_fail(ctx, e, "sync");
+  const size_t cells = (size_t)W * W, roots_b = (size_t)W * kNode;
+  BatchOps ops{ctx, b};
+  std::unique_ptr<BatchPasses> plan;
+  cel_status st = run_passes(ops, hm, first_row_pass_batch(hm, n, k), plan, hm, n, k);
+  if (st != CEL_OK) return st;
   // The verdicts, square by square. A replay (repair_exact) reuses the single-square prefix of
   // the slots and of the stage, so the batch's results leave the stage first.
-  const std::vector<uint8_t> got_all(b.hroots, b.hroots + 2 * roots_b);
+  const std::vector<uint8_t> got_all(b.hroots, b.hroots + 2 * n * roots_b);
   const std::vector<int32_t> flags_all(b.hflags, b.hflags + (size_t)n * 2 * W);
-  std::vector<uint8_t> got(2 * (size_t)W * kNode);
+  std::vector<uint8_t> got(2 * roots_b);
   for (uint32_t i = 0; i < n; i++) {
-    SquarePasses& sq = bp.sq[i];
-    const uint8_t* const exp[2] = {row_roots + (size_t)i * W * kNode, col_roots + (size_t)i * W * kNode};
     square_roots(got_all.data(), n, W, i, got.data());
     std::vector<uint8_t> m(hm.begin() + (ptrdiff_t)(i * cells), hm.begin() + (ptrdiff_t)((i + 1) * cells));
-    const RepairOut o = out.of(i, W);
     RepairBufs one = b.one;
     one.eds = b.eds + i * cells * kShare;
-    cel_status code;
-    const long f = first_failure(sq.order.data(), sq.order.size(), {got.data(), kNode, RootRecords::BY_AXIS}, exp,
-                                 flags_all.data() + (size_t)i * 2 * W, W, &code);
-    if (f >= 0) {
-      const Check& c = sq.order[(size_t)f];
-      if (c.kind == Check::SANITY) {
-        st = fail_axis(ctx, one, m, o, code, c.is_col, c.idx, false);
-      } else {  // the order decides which axis fails first: this square again, alone, in rsmt2d's order
-        if ((st = repair_bufs(ctx, k, false, &one)) != CEL_OK) return st;
-        st = repair_exact(ctx, one, m, k, exp[0], exp[1], o);
-      }
-    } else if (!sq.solved()) {
-      rollback(m, W, sq.solves, sq.solves.size());
-      st = fail(ctx, CEL_EUNREPAIRABLE, "failed to solve data square");
-    } else {
-      std::fill(m.begin(), m.end(), (uint8_t)1);
-      st = CEL_OK;
-    }
-    if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
-    if (st != CEL_OK && first_error->empty()) *first_error = "square " + std::to_string(i) + ": " + ctx->last_error;
-    out.status[i] = st;
+    st = verdict(ctx, one, plan->sq[i], got.data(), flags_all.data() + (size_t)i * 2 * W, row_roots + i * roots_b,
+                 col_roots + i * roots_b, m, out.of(i, W));
+    if (!out.record(ctx, i, st, first_error)) return st;
     std::memcpy(hm.data() + i * cells, m.data(), cells);
   }
   return CEL_OK;
@@ -957,9 +841,7 @@ static cel_status repair_batch_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds,
       st = repair_locked(ctx, h_eds ? h_eds + i * eds_b : nullptr, d_eds ? static_cast<uint8_t*>(d_eds) + i * eds_b : nullptr,
                          present + i * cells, k, share_size, row_roots + (size_t)i * W * kNode,
                          col_roots + (size_t)i * W * kNode, out.of(i, W));
-      if (st != CEL_OK && st != CEL_EBYZANTINE && st != CEL_EBADROOT && st != CEL_EUNREPAIRABLE) return st;
-      if (st != CEL_OK && first_error.empty()) first_error = "square " + std::to_string(i) + ": " + ctx->last_error;
-      out.status[i] = st;
+      if (!out.record(ctx, i, st, &first_error)) return st;
     }
     if (!first_error.empty()) ctx->last_error = first_error;
     return CEL_OK;
@@ -968,7 +850,9 @@ static cel_status repair_batch_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds,
     if (bad) std::fill(bad, bad + n, -1);
   DeviceGuard g(ctx->device);
   BatchBufs b{};
-  if ((st = batch_bufs(ctx, k, n, &b)) != CEL_OK) return st;
+  b.W = b.one.W = W;
+  b.n = n;
+  if ((st = carve_bufs(ctx, kBatchSlots, carve_batch_stage, &b)) != CEL_OK) return st;
   hipError_t e = hipSuccess;
   b.eds = static_cast<uint8_t*>(d_eds);
   if (!d_eds) {
@@ -988,6 +872,8 @@ static cel_status repair_batch_locked(cel_ctx* ctx, uint8_t* h_eds, void* d_eds,
 }
 
 }  // namespace
+
+extern "C" {
 
 cel_status cel_repair(cel_ctx* ctx, uint8_t* eds, uint8_t* present, uint32_t k, uint32_t share_size,
                       const uint8_t* row_roots, const uint8_t* col_roots, int32_t* bad_axis, int32_t* bad_index,
@@ -1033,18 +919,10 @@ cel_status cel_dev_repair(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t 
 
 size_t cel_dev_repair_batch_scratch_size(uint32_t k, uint32_t n) {
   if (!k || (k & (k - 1)) || k > 512 || n == 0) return 0;
-  size_t total = 0;
-  if (!batch_merged(k, n)) {  // one square at a time
-    RepairBufs b{};
-    b.W = 2 * k;
-    for (auto walk : {carve_in, carve_aux, carve_mask, carve_work, carve_roots}) total += carved(walk, nullptr, b);
-    return total;
-  }
   BatchBufs b{};
   b.W = b.one.W = 2 * k;
   b.n = n;
-  for (const auto& s : kBatchSlots) total += carved(s.walk, nullptr, b);
-  return total;
+  return batch_merged(k, n) ? slots_size(kBatchSlots, b) : slots_size(kSquareSlots, b.one);  // else one square at a time
 }
 
 cel_status cel_dev_repair_batch(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32_t n, uint32_t k,

@@ -1,9 +1,10 @@
 // The repair's host planner (api_repair.cpp): everything rsmt2d's Repair decides from the
 // presence mask alone. The pass-parallel schedule's bookkeeping (MaskBits), rsmt2d's own
 // sweep order (plan_sweeps), the log of checks both leave behind and its replay over the
-// roots and flags the device sends back, and the merged schedule of a batch of squares
-// (BatchPasses). Plain C++ with no HIP in it: tools/repair_plan_check.cpp and
-// tools/repair_batch_plan_check.cpp include this header alone and walk it on the host.
+// roots and flags the device sends back, and the pass schedule as a stepper, of one square
+// (SquarePasses) and merged over a batch of squares (BatchPasses): the repair drives either
+// through the same next() / apply(). Plain C++ with no HIP in it: tools/repair_plan_check.cpp
+// and tools/repair_batch_plan_check.cpp include this header alone and step it on the host.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -311,40 +312,65 @@ inline std::vector<int32_t> first_row_pass_batch(const std::vector<uint8_t>& mas
   return first;
 }
 
-// One square's pass schedule as a stepper: the lists come from the counts, apply() is the
-// sequential view of the pass (fill_pass, log_pass), as repair_core takes them one by one.
+// One square's pass schedule as a stepper: every solvable row, then every solvable column,
+// until the square is solved or stuck. The constructor builds the bitsets and the sanity
+// checks (preRepairSanityCheck: for i: row i, column i; they open `order`). next() gives the
+// next non-empty pass from the counts alone (cheap: the caller enqueues its decode at once);
+// apply() is then the sequential view of that pass (fill_pass, log_pass) and gives the
+// orthogonal axes it completed, in direction !is_col. Plain axis indices, as the
+// single-square kernels read them.
 struct SquarePasses {
   uint32_t k, W;
   MaskBits mb;
+  std::vector<int32_t> sanity[2];  // the axes complete at the start, by direction
   std::vector<Check> order;
   std::vector<Solve> solves;
-  std::vector<std::vector<int32_t>> by_solve;
-  SquarePasses(const uint8_t* hm, uint32_t k_) : k(k_), W(2 * k_), mb(hm, 2 * k_) {}
-  bool solved() const { return mb.total == (uint64_t)W * W; }
-  // preRepairSanityCheck: for i: row i, column i. Appends the checks; comp = the complete axes.
-  void sanity(std::vector<int32_t> comp[2]) {
+  std::vector<int32_t> cur;                    // the pass solvable() found last
+  std::vector<std::vector<int32_t>> by_solve;  // the orthogonal axes each of its solves completed
+  SquarePasses(const uint8_t* hm, uint32_t k_) : k(k_), W(2 * k_), mb(hm, 2 * k_) {
     for (uint32_t i = 0; i < W; i++)
       for (int is_col = 0; is_col < 2; is_col++)
         if (mb.cnt[is_col][i] == W) {
           order.push_back({Check::SANITY, is_col, (int32_t)i, -1});
-          comp[is_col].push_back((int32_t)i);
+          sanity[is_col].push_back((int32_t)i);
         }
   }
-  void solvable(int is_col, std::vector<int32_t>& list) const {
-    list.clear();
+  bool solved() const { return mb.total == (uint64_t)W * W; }
+  // cur = what a pass in direction is_col solves now; false when that is nothing. A batch
+  // asks every square for the direction of the merged pass.
+  bool solvable(int is_col) {
+    dir = is_col;
+    cur.clear();
+    if (solved()) return false;
     for (uint32_t i = 0; i < W; i++)
-      if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) list.push_back((int32_t)i);
+      if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) cur.push_back((int32_t)i);
+    return !cur.empty();
   }
-  void apply(int is_col, const std::vector<int32_t>& list, std::vector<int32_t>& orth) {
-    mb.fill_pass(is_col, list, by_solve);
-    log_pass(is_col, list, by_solve, order, solves, orth);
+  // false: solved or stuck
+  bool next(int* is_col, std::vector<int32_t>& list) {
+    for (uint32_t tries = 0; tries < 2; tries++) {
+      if (solvable(dir)) {
+        *is_col = dir;
+        list = cur;
+        return true;
+      }
+      dir ^= 1;
+    }
+    return false;
   }
+  void apply(std::vector<int32_t>& orth) {
+    mb.fill_pass(dir, cur, by_solve);
+    log_pass(dir, cur, by_solve, order, solves, orth);
+    dir ^= 1;
+  }
+
+ private:
+  int dir = 0;  // direction of cur, then of the pass next() looks at first
 };
 
-// The merged schedule of n squares, pass by pass. next() gives the next non-empty global pass
-// from the counts alone (cheap: the caller enqueues its decode at once); apply() then runs
-// every listed square's bookkeeping and gives the orthogonal axes the pass completed, packed,
-// in direction !is_col. Serial per square.
+// The merged schedule of n squares, pass by pass, with SquarePasses' surface: next() gives the
+// next non-empty global pass, apply() runs every listed square's bookkeeping. Entries, sanity
+// lists and orthogonal axes are packed. Serial per square.
 struct BatchPasses {
   uint32_t n, k, W;
   std::vector<SquarePasses> sq;
@@ -352,26 +378,19 @@ struct BatchPasses {
   BatchPasses(const std::vector<uint8_t>& masks, uint32_t n_, uint32_t k_) : n(n_), k(k_), W(2 * k_) {
     const size_t cells = (size_t)W * W;
     sq.reserve(n);
-    std::vector<int32_t> comp[2];
     for (uint32_t q = 0; q < n; q++) {
       sq.emplace_back(masks.data() + q * cells, k);
-      comp[0].clear();
-      comp[1].clear();
-      sq.back().sanity(comp);
       for (int d = 0; d < 2; d++)
-        for (int32_t i : comp[d]) sanity[d].push_back(pack_entry(q, (uint32_t)i, d));
+        for (int32_t i : sq[q].sanity[d]) sanity[d].push_back(pack_entry(q, (uint32_t)i, d));
     }
-    lists.resize(n);
   }
   // false: no square has anything left to solve (each is solved or stuck)
   bool next(int* is_col, std::vector<int32_t>& entries) {
     for (uint32_t tries = 0; tries < 2; tries++, dir ^= 1) {
       entries.clear();
-      for (uint32_t q = 0; q < n; q++) {
-        lists[q].clear();
-        if (!sq[q].solved()) sq[q].solvable(dir, lists[q]);
-        for (int32_t i : lists[q]) entries.push_back(pack_entry(q, (uint32_t)i, dir));
-      }
+      for (uint32_t q = 0; q < n; q++)
+        if (sq[q].solvable(dir))
+          for (int32_t i : sq[q].cur) entries.push_back(pack_entry(q, (uint32_t)i, dir));
       if (!entries.empty()) {
         *is_col = dir;
         return true;
@@ -383,16 +402,15 @@ struct BatchPasses {
     orth.clear();
     std::vector<int32_t> o;
     for (uint32_t q = 0; q < n; q++) {
-      if (lists[q].empty()) continue;
-      sq[q].apply(dir, lists[q], o);
+      if (sq[q].cur.empty()) continue;
+      sq[q].apply(o);
       for (int32_t j : o) orth.push_back(pack_entry(q, (uint32_t)j, !dir));
     }
     dir ^= 1;
   }
 
  private:
-  int dir = 0;                              // direction of the pass next() looks at first
-  std::vector<std::vector<int32_t>> lists;  // the pass next() gave, by square
+  int dir = 0;  // direction of the pass next() looks at first
 };
 
 // Square i's root records, [2][W] by (direction, axis) as first_failure reads them BY_AXIS, out

@@ -12,9 +12,10 @@
 // 3. each square's projection of the merged passes (direction, axes, completed orthogonal
 //    axes) is its own schedule, taken from a byte mask filled cell by cell; a complete square
 //    and one stuck at the start are in no pass;
-// 4. each square's check order and solve log are those of the single-square loop (MaskBits,
-//    fill_pass, log_pass as repair_core drives them), and rollback over its own log gives the
-//    byte mask before solve t for t = 0, the middle, the end;
+// 4. each square's check order and solve log are those of the square stepped alone (its own
+//    SquarePasses, as the single repair steps it; tools/repair_plan_check.cpp checks that one
+//    against the byte mask), and rollback over its own log gives the byte mask before solve t
+//    for t = 0, the middle, the end;
 // 5. the verdicts over synthetic results in the batch's layout ([n][W] row roots, [n][W] column
 //    roots, flags [n][2][W]): one square fails (a root, or a flag) at a check of its order, the
 //    others pass, for every choice of the failing square.
@@ -129,28 +130,13 @@ static std::vector<OwnPass> own_schedule(std::vector<uint8_t> m, uint32_t W) {
   return out;
 }
 
-// The single-square loop as repair_core drives it: the check order and the solve log.
-static void single_logs(const std::vector<uint8_t>& hm, uint32_t W, std::vector<Check>& order, std::vector<Solve>& solves) {
-  const uint32_t k = W / 2;
-  MaskBits mb(hm, W);
-  for (uint32_t i = 0; i < W; i++)
-    for (int is_col = 0; is_col < 2; is_col++)
-      if (mb.cnt[is_col][i] == W) order.push_back({Check::SANITY, is_col, (int32_t)i, -1});
+// The square alone, stepped as the single repair steps it: the check order and the solve log.
+static SquarePasses single_logs(const std::vector<uint8_t>& hm, uint32_t W) {
+  SquarePasses sp(hm.data(), W / 2);
   std::vector<int32_t> list, orth;
-  std::vector<std::vector<int32_t>> by_solve;
-  for (;;) {
-    bool progress = false;
-    for (int is_col = 0; is_col < 2; is_col++) {
-      list.clear();
-      for (uint32_t i = 0; i < W; i++)
-        if (mb.cnt[is_col][i] >= k && mb.cnt[is_col][i] < W) list.push_back((int32_t)i);
-      if (list.empty()) continue;
-      mb.fill_pass(is_col, list, by_solve);
-      log_pass(is_col, list, by_solve, order, solves, orth);
-      progress = true;
-    }
-    if (mb.total == (uint64_t)W * W || !progress) break;
-  }
+  int is_col;
+  while (sp.next(&is_col, list)) sp.apply(orth);
+  return sp;
 }
 
 static bool same(const std::vector<Check>& a, const std::vector<Check>& b) {
@@ -226,10 +212,11 @@ static void check_batch(const std::vector<std::vector<uint8_t>>& all, const std:
       }
     if (!any_solvable) CHECK(proj[q].empty());
     // 4. the logs and the rollback
-    std::vector<Check> order;
-    std::vector<Solve> solves;
-    single_logs(hm, W, order, solves);
+    const SquarePasses alone = single_logs(hm, W);
+    const std::vector<Check>& order = alone.order;
+    const std::vector<Solve>& solves = alone.solves;
     const SquarePasses& sq = bp.sq[q];
+    CHECK(sq.sanity[0] == alone.sanity[0] && sq.sanity[1] == alone.sanity[1]);
     CHECK(same(sq.order, order));
     CHECK(sq.solves.size() == solves.size());
     for (size_t t = 0; t < solves.size() && t < sq.solves.size(); t++)

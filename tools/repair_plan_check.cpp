@@ -5,11 +5,11 @@
 // For every width W = 2 .. 256 (one partial word, exactly one word, several words) it takes
 // random masks at survival p = 0.3, 0.5, 0.55, 0.7, 0.9 (splitmix64 by cell index, fixed seeds)
 // and the structured masks of the GPU tests (one quadrant only, the left half, all but one
-// cell, all present), and runs the pass schedule over each as the repair does, beside a byte
-// mask on which every solve is applied cell by cell:
+// cell, all present), and steps the repair's own pass schedule (SquarePasses: next, apply) over
+// each, beside a byte mask on which every solve is applied cell by cell:
 // 1. the first-row scan = {i : k <= known cells of row i < W};
-// 2. every pass's list, and after every fill_pass cnt[0], cnt[1], total and both bitsets,
-//    against a recount of the byte mask;
+// 2. the sanity lists and checks, every pass's direction and list, and after every apply
+//    cnt[0], cnt[1], total and both bitsets, against a recount of the byte mask;
 // 3. orth[t] = the orthogonal axes whose last missing cell solve t filled, ascending;
 // 4. closure: the passes and plan_sweeps end with the same `solved` and the same known cells;
 // 5. rollback(hm, W, solves, t) = the byte mask before solve t, for t = 0, the middle, the end.
@@ -127,14 +127,27 @@ static void check_mask(const std::vector<uint8_t>& hm, uint32_t W, Counts* n) {
     if (c >= k && c < W) want_first.push_back((int32_t)i);
   }
   CHECK(first_row_pass(hm, k) == want_first);
-  // 2, 3. the passes, as repair_core takes them
-  MaskBits mb(hm, W);
+  // 2, 3. the passes: the repair's stepper beside the rounds (rows, then columns) of the byte mask
+  SquarePasses sp(hm.data(), k);
+  const MaskBits& mb = sp.mb;
+  const std::vector<Check>& order = sp.order;
+  const std::vector<Solve>& solves = sp.solves;
   std::vector<uint8_t> m(hm);
   check_bits(mb, m);
-  std::vector<Check> order;
-  std::vector<Solve> solves;
-  std::vector<int32_t> list, orth;
-  std::vector<std::vector<int32_t>> by_solve;
+  // the sanity checks: for i: row i, column i, every complete axis; they open the order
+  std::vector<int32_t> want_sanity[2];
+  size_t nsanity = 0;
+  for (uint32_t i = 0; i < W; i++)
+    for (int d = 0; d < 2; d++) {
+      if (known(m, W, d, i) != W) continue;
+      want_sanity[d].push_back((int32_t)i);
+      CHECK(nsanity < order.size() && order[nsanity].kind == Check::SANITY && order[nsanity].is_col == d &&
+            order[nsanity].idx == (int32_t)i && order[nsanity].solve == -1);
+      nsanity++;
+    }
+  CHECK(order.size() == nsanity && sp.sanity[0] == want_sanity[0] && sp.sanity[1] == want_sanity[1]);
+  std::vector<int32_t> list, got_list, orth;
+  int got_col = -1;
   bool solved = false, first = true;
   for (;;) {
     bool progress = false;
@@ -145,8 +158,11 @@ static void check_mask(const std::vector<uint8_t>& hm, uint32_t W, Counts* n) {
         if (c >= k && c < W) list.push_back((int32_t)i);
       }
       if (first && !is_col) CHECK(list == want_first);  // the pass the repair issues early
-      if (list.empty()) continue;
+      if (list.empty()) continue;  // the stepper skips an empty pass
       first = false;
+      const bool stepped = sp.next(&got_col, got_list);
+      CHECK(stepped && got_col == is_col && got_list == list);
+      if (!stepped) return;
       std::vector<std::vector<int32_t>> want_orth;
       std::vector<int32_t> all_orth;
       for (int32_t i : list) {
@@ -154,11 +170,10 @@ static void check_mask(const std::vector<uint8_t>& hm, uint32_t W, Counts* n) {
         all_orth.insert(all_orth.end(), want_orth.back().begin(), want_orth.back().end());
       }
       std::sort(all_orth.begin(), all_orth.end());
-      mb.fill_pass(is_col, list, by_solve);
-      CHECK(by_solve == want_orth);
-      check_bits(mb, m);
       const size_t o0 = order.size(), s0 = solves.size();
-      log_pass(is_col, list, by_solve, order, solves, orth);
+      sp.apply(orth);
+      CHECK(sp.by_solve == want_orth);
+      check_bits(mb, m);
       CHECK(orth == all_orth);
       CHECK(solves.size() == s0 + list.size() && order.size() == o0 + list.size() + all_orth.size());
       n->passes++;
@@ -171,8 +186,9 @@ static void check_mask(const std::vector<uint8_t>& hm, uint32_t W, Counts* n) {
     }
     if (!progress) break;
   }
+  CHECK(!sp.next(&got_col, got_list) && sp.solved() == solved);
   // the log: every SOLVE names its own solve, followed by its ORTH axes
-  for (size_t o = 0, s = 0; o < order.size(); o++) {
+  for (size_t o = nsanity, s = 0; o < order.size(); o++) {
     if (order[o].kind == Check::SOLVE) {
       CHECK(s < solves.size() && order[o].solve == (int32_t)s && order[o].idx == solves[s].idx &&
             order[o].is_col == solves[s].is_col);
