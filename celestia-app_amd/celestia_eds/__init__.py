@@ -11,4 +11,4 @@ fraud proofs (celestia-node's share/eds/byzantine).
 from . import _lib, blob, block, da, fraud, rsmt2d, wrapper  # noqa: F401
 from .blob import Blob, parse_sparse_shares  # noqa: F401
 from ._lib import CelError, Context, default_context, load  # noqa: F401
-from .block import ExtendBlock, PrepareProposal, ProcessProposal  # noqa: F401
+from .block import ExtendBlock, ExtendBlocks, PrepareProposal, ProcessProposal, ProcessProposals  # noqa: F401

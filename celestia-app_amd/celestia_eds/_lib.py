@@ -44,6 +44,7 @@ EXPORTS = [
     "cel_create_commitments", "cel_dev_commitments_workspace_size", "cel_dev_create_commitments",
     "cel_blob_tx_commitments", "cel_blob_subtree_sizes",
     "cel_square_layout", "cel_dev_square_build", "cel_block_extend",
+    "cel_dev_square_build_batch", "cel_block_extend_batch", "cel_block_batch_error",
     "cel_extend_sharded", "cel_shard_plan_create", "cel_shard_plan_destroy", "cel_shard_plan_transport",
     "cel_shard_plan_last_error", "cel_shard_plan_note", "cel_shard_plan_time_exchange", "cel_shard_plan_upload", "cel_shard_plan_run", "cel_shard_plan_wait",
     "cel_extend_batch_multi", "cel_probe_sha256", "cel_probe_hbm_copy", "cel_probe_hbm_stream",
@@ -138,6 +139,10 @@ def load():
             "cel_square_layout": (i32, [P, P, u32, u32, u32, u32, P, P, P, u32, P, P, u32, P]),
             "cel_dev_square_build": (i32, [P, P, P, u32, P, u32, u32, P, P]),
             "cel_block_extend": (i32, [P, P, P, u32, u32, u32, u32, P, P, P, P, P, P, u64, P, P, u32, P, u32]),
+            "cel_dev_square_build_batch": (i32, [P, P, P, u32, P, P, P, P, P, P, P, P]),
+            "cel_block_extend_batch": (i32, [P, P, P, P, u32, u32, u32, u32, u32, u64, P, P, P, P, P, P, u64, P, P, P, P,
+                                             u32, P, P, u32]),
+            "cel_block_batch_error": (ctypes.c_char_p, [P, u32]),
             "cel_extend_sharded": (i32, [P, u32, P, u32, u32, P, P, P, P, u32]),
             "cel_shard_plan_create": (i32, [P, u32, u32, u32, PP]),
             "cel_shard_plan_destroy": (None, [P]),

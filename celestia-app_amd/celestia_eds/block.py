@@ -10,6 +10,10 @@ hashes the roots, and the blob share commitments come from the same upload.
   PrepareProposal(ctx, txs)                app/prepare_proposal.go:48-92: square.Build (txs
       that do not fit are dropped) and the data root -> (kept txs, k, data root)
 
+  ExtendBlocks(ctx, blocks) / ProcessProposals(ctx, blocks, data_hashes)   the first two for a
+      range of blocks in one call (cel_block_extend_batch): a DataAvailabilityHeader, or
+      (accept, commitments), per block
+
 The defaults are appconsts SquareSizeUpperBound = 128 and SubtreeRootThreshold = 64.
 """
 import ctypes
@@ -106,6 +110,103 @@ def ProcessProposal(ctx, txs, data_hash, max_square_size=SQUARE_SIZE_UPPER_BOUND
             return False, []
         raise
     return b.dah == bytes(data_hash), b.commitments
+
+
+def block_extend_batch(ctx, blocks, max_square_size=SQUARE_SIZE_UPPER_BOUND,
+                       subtree_root_threshold=SUBTREE_ROOT_THRESHOLD, greedy=False, want_commitments=False,
+                       flags=_lib.FLAG_ORDER_CHECK, host_threads=1, max_eds_bytes=0):
+    """cel_block_extend_batch over blocks (a list of tx lists) -> a list of the objects
+    block_extend returns (eds None), one per block. A block that failed carries its .status and
+    .error (k 0, no roots, a zero dah, commitments []); the others carry status 0 and error "".
+    Argument and device errors raise."""
+    ctx = ctx or _lib.default_context()
+    l = ctx.lib
+    blocks = [[bytes(t) for t in b] for b in blocks]
+    n = len(blocks)
+    flat = [t for b in blocks for t in b]
+    lens = np.array([len(t) for t in flat] + [0], np.uint32)
+    nt = np.array([len(b) for b in blocks] + [0], np.uint32)
+    raw = b"".join(flat)
+    buf = ctypes.create_string_buffer(raw, max(len(raw), 1))
+    k = np.zeros(max(n, 1), np.uint32)
+    status = np.zeros(max(n, 1), np.int32)
+    included = np.zeros(max(len(flat), 1), np.uint8)
+    cap = n * 2 * max_square_size
+    rr = np.zeros((max(cap, 1), _lib.NMT_NODE_SIZE), np.uint8)
+    cr = np.zeros((max(cap, 1), _lib.NMT_NODE_SIZE), np.uint8)
+    root_off = np.zeros(n + 1, np.uint32)
+    dah = np.zeros((max(n, 1), 32), np.uint8)
+    ccap, ncom = 0, ctypes.c_uint32()
+    if want_commitments:  # cap = 0 only counts the blobs (no device work)
+        ctx.check(l.cel_blob_tx_commitments(ctx.handle, buf, _p(lens), len(flat), subtree_root_threshold, None, None, 0,
+                                            ctypes.byref(ncom)))
+        ccap = ncom.value
+    com = np.zeros((max(ccap, 1), 32), np.uint8)
+    cblock = np.zeros(max(ccap, 1), np.uint32)
+    ctx_index = np.zeros(max(ccap, 1), np.uint32)
+    st = l.cel_block_extend_batch(ctx.handle, buf, _p(lens), _p(nt), n, max_square_size, subtree_root_threshold,
+                                  1 if greedy else 0, host_threads, max_eds_bytes, _p(k), _p(status), _p(included),
+                                  _p(rr), _p(cr), _p(root_off), cap, _p(dah), _p(com) if ccap else None,
+                                  _p(cblock) if ccap else None, _p(ctx_index) if ccap else None, ccap,
+                                  ctypes.byref(ncom), None, flags)
+    # the first failed block's status is the call's too: anything else (an argument or device
+    # error, after which the per-block outputs may not be written) raises
+    failed = [int(s) for s in status[:n] if s != 0]
+    if st != _lib.OK and (not failed or st != failed[0] or not l.cel_last_error(ctx.handle).startswith(b"block ")):
+        ctx.check(st)
+    out, t0 = [], 0
+    for i, txs in enumerate(blocks):
+        b = _Block()
+        b.status = int(status[i])
+        b.error = l.cel_block_batch_error(ctx.handle, i).decode() if b.status else ""
+        b.k = int(k[i])
+        b.included = [int(x) for x in included[t0:t0 + len(txs)]]
+        t0 += len(txs)
+        r0 = int(root_off[i])
+        b.row_roots, b.col_roots = rr[r0:r0 + 2 * b.k].copy(), cr[r0:r0 + 2 * b.k].copy()
+        b.dah = dah[i].tobytes()
+        b.eds = None
+        b.commitments = [] if want_commitments else None
+        b.txs = txs
+        out.append(b)
+    if want_commitments:
+        for j in range(ncom.value):
+            out[int(cblock[j])].commitments.append((int(ctx_index[j]), com[j].tobytes()))
+    return out
+
+
+def ExtendBlocks(ctx, blocks, max_square_size=SQUARE_SIZE_UPPER_BOUND, subtree_root_threshold=SUBTREE_ROOT_THRESHOLD,
+                 host_threads=1):
+    """app.ExtendBlock over a range of blocks in one call -> a DataAvailabilityHeader per block
+    (no EDS comes back); raises CelError with go-square's message, prefixed "block <i>: ", for
+    the first block whose txs do not construct a square."""
+    out = []
+    for i, b in enumerate(block_extend_batch(ctx, blocks, max_square_size, subtree_root_threshold,
+                                             host_threads=host_threads)):
+        if b.status:
+            raise _lib.CelError(b.status, f"block {i}: {b.error}")
+        dah = DataAvailabilityHeader([r.tobytes() for r in b.row_roots], [c.tobytes() for c in b.col_roots])
+        dah.hash = b.dah
+        out.append(dah)
+    return out
+
+
+def ProcessProposals(ctx, blocks, data_hashes, max_square_size=SQUARE_SIZE_UPPER_BOUND,
+                     subtree_root_threshold=SUBTREE_ROOT_THRESHOLD, host_threads=1):
+    """ProcessProposal over a range of blocks in one call -> [(accept, commitments)] per block,
+    by ProcessProposal's rule: a block that does not construct or whose commitments cannot be
+    computed is (False, []); any other block status raises."""
+    out = []
+    for i, (b, want) in enumerate(zip(block_extend_batch(ctx, blocks, max_square_size, subtree_root_threshold,
+                                                         want_commitments=True, host_threads=host_threads),
+                                      data_hashes)):
+        if b.status in (_lib.EINVAL, _lib.ETOOBIG, _lib.EORDER):
+            out.append((False, []))
+        elif b.status:
+            raise _lib.CelError(b.status, f"block {i}: {b.error}")
+        else:
+            out.append((b.dah == bytes(want), b.commitments))
+    return out
 
 
 def PrepareProposal(ctx, txs, max_square_size=SQUARE_SIZE_UPPER_BOUND, subtree_root_threshold=SUBTREE_ROOT_THRESHOLD):

@@ -264,6 +264,15 @@ hipError_t launch_blob_commit(const uint8_t* d_data, const blob::Plan& plan, voi
 // compact shares (16-byte aligned), d_txs the tx bytes the BLOB segments point into.
 hipError_t launch_square_build(const uint8_t* d_txs, const cel_square_segment* d_segs, const uint32_t* d_share_seg,
                                const uint8_t* d_compact, uint8_t* d_eds, uint32_t k, hipStream_t s);
+// The same for every block of a chunk in one launch (block_batch_plan.hpp): the blocks' plans
+// concatenated, d_share_seg entries chunk-wide segment indices, d_seg_block the block of each
+// segment, d_recs a bb::BlockRec per block; total_shares * 32 lanes, below 2^32.
+namespace bb {
+struct BlockRec;
+}
+hipError_t launch_square_build_batch(const uint8_t* d_txs, const cel_square_segment* d_segs, const uint32_t* d_share_seg,
+                                     const uint32_t* d_seg_block, const bb::BlockRec* d_recs, const uint8_t* d_compact,
+                                     uint8_t* d_eds, uint32_t total_shares, hipStream_t s);
 
 // Erasure decode of `naxes` axes of 2n shards each, gathered into a dense
 // [naxes][2n][len] buffer with a [naxes][2n] present mask. In place.
@@ -365,6 +374,9 @@ struct cel_ctx {
   cel::StagedUpload plan_up, square_up;
   hipEvent_t ev_sq_done = nullptr;
   bool sq_built = false;
+  // The last cel_block_extend_batch on this ctx: each block's message ("" where it is CEL_OK),
+  // for cel_block_batch_error.
+  std::vector<std::string> block_errors;
   // Schedule fuzzing of the repair's two streams (cel_debug_schedule_fuzz; tests only):
   // before each enqueue point, an idle kernel of 0..fuzz_max_us microseconds.
   uint64_t fuzz_state = 0;

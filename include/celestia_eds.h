@@ -994,6 +994,64 @@ cel_status cel_block_extend(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx
                             uint32_t* commit_tx_index, uint32_t commit_cap, uint32_t* n_commit,
                             uint32_t flags);
 
+/* ------------------------------------------- a range of blocks from txs (one call)
+ * The block path for a range of heights: a node catching up holds each block's txs and needs
+ * each block's data root and DAH. Blocks that construct are grouped by square width, cut into
+ * chunks whose EDS bytes fit a budget, and each chunk costs one upload of its blob bytes and
+ * plan, one square-build launch for all its blocks, one extension and one commit per width
+ * present, one commitments batch and one download; one stream synchronise ends the call.
+ *
+ * cel_dev_square_build_batch: cel_dev_square_build for n_blocks blocks in one launch. d_txs:
+ * device tx bytes, block b's txs starting at d_txs + tx_base[b] (its BLOB offsets count from
+ * there); segments: the blocks' layouts back to back, n_segments[b] of block b; compact: their
+ * compact shares back to back, n_compact_shares[b] of block b (NULL if there are none);
+ * k[b]: block b's width; d_eds: one device buffer, 16-byte aligned, in which block b's EDS of
+ * 2k*2k*512 bytes starts at byte eds_off[b] (a multiple of 16; the caller keeps the EDSs
+ * apart). Exactly quadrant Q0 of every block's EDS is written, every byte of it. Every block's
+ * layout is checked as cel_dev_square_build checks one, before any device work; the blocks
+ * hold fewer than 2^27 shares in all. Asynchronous on stream (NULL = ctx's stream). */
+cel_status cel_dev_square_build_batch(cel_ctx* ctx, const void* d_txs, const uint64_t* tx_base,
+                                      uint32_t n_blocks, const cel_square_segment* segments,
+                                      const uint32_t* n_segments, const uint8_t* compact,
+                                      const uint32_t* n_compact_shares, const uint32_t* k,
+                                      void* d_eds, const uint64_t* eds_off, void* stream);
+/* cel_block_extend_batch: cel_block_extend for n_blocks blocks. txs: every block's txs
+ * concatenated, block after block; tx_lens: their lengths; block_ntx[n_blocks]: how many of
+ * them belong to each block. max_square_size, subtree_root_threshold, greedy, flags: as
+ * cel_block_extend, the same for every block.
+ * host_threads: the blocks are laid out on up to this many threads (0 and 1: the calling
+ * thread). max_eds_bytes: the EDS bytes of one chunk (0: 2 GiB); a block above it is a chunk
+ * of its own.
+ * Per block i: k_out[i]; status_out[i]; included (nullable), one byte per tx in tx order
+ * across blocks; dah + 32 i; row_roots / col_roots (roots_cap nodes of 90 bytes each): block
+ * i's 2k roots of each start at node root_off[i], and root_off[n_blocks] is the total
+ * (n_blocks * 2 * max_square_size always suffices; a cap below the total is CEL_EINVAL).
+ * commitments / commit_block / commit_tx_index / commit_cap / n_commit: every blob of every
+ * BlobTx of every block that constructed, flat in block order, with its block and its tx's
+ * index inside the block; cel_block_extend's convention (*n_commit always receives the count,
+ * commit_cap == 0 skips them, a cap below the count is CEL_EINVAL).
+ * A block whose txs do not construct, or whose commitments cannot be computed, gets the
+ * status cel_block_extend gives it, k 0, no roots, a zero dah, zero included bytes and no
+ * commitments; it does not stop the others, whose outputs are exactly cel_block_extend's. The
+ * call returns the first status in block order that is not CEL_OK, with that block's message
+ * prefixed "block <i>: " in cel_last_error; cel_block_batch_error gives any block's message.
+ * Argument errors, both caps among them, return before any output but *n_commit is written.
+ * phase_ms (nullable, 2 floats): the host layout's wall time and the device time between
+ * events around the call's enqueued work, in milliseconds. */
+cel_status cel_block_extend_batch(cel_ctx* ctx, const uint8_t* txs, const uint32_t* tx_lens,
+                                  const uint32_t* block_ntx, uint32_t n_blocks,
+                                  uint32_t max_square_size, uint32_t subtree_root_threshold,
+                                  uint32_t greedy, uint32_t host_threads, uint64_t max_eds_bytes,
+                                  uint32_t* k_out, int32_t* status_out, uint8_t* included,
+                                  uint8_t* row_roots, uint8_t* col_roots, uint32_t* root_off,
+                                  uint64_t roots_cap, uint8_t* dah, uint8_t* commitments,
+                                  uint32_t* commit_block, uint32_t* commit_tx_index,
+                                  uint32_t commit_cap, uint32_t* n_commit, float* phase_ms,
+                                  uint32_t flags);
+/* The message of block `block` of the last cel_block_extend_batch on ctx ("" if it was
+ * CEL_OK or there is no such block); valid until the next call on ctx. */
+const char* cel_block_batch_error(cel_ctx* ctx, uint32_t block);
+
 #ifdef __cplusplus
 }
 #endif
