@@ -56,6 +56,9 @@ EXPORTS = [
     "cel_dev_namespace_workspace_size", "cel_dev_namespace_plan", "cel_dev_namespace_prove", "cel_namespace_rows",
     "cel_nmt_verify_namespace_batch", "cel_dev_nmt_verify_namespace_workspace_size",
     "cel_dev_nmt_verify_namespace_batch",
+    "cel_dev_tree_index_batch_size", "cel_dev_tree_index_build_batch", "cel_dev_prove_squares_workspace_size",
+    "cel_dev_prove_squares", "cel_dev_namespace_squares_workspace_size", "cel_dev_namespace_plan_squares",
+    "cel_dev_namespace_prove_squares", "cel_prove_samples_squares", "cel_namespace_rows_squares",
     "cel_dev_blobs_workspace_size", "cel_dev_blobs_plan", "cel_dev_blobs_emit", "cel_blobs_by_range",
     "cel_namespace_ods_ranges",
     "cel_dev_txs_workspace_size", "cel_dev_txs_plan", "cel_dev_txs_emit", "cel_txs_by_range",
@@ -175,6 +178,15 @@ def load():
             "cel_dev_namespace_plan": (i32, [P, P, u32, u32, P, u64, P, P, P, P, P, P, P, P, P, P]),
             "cel_dev_namespace_prove": (i32, [P, P, P, u32, u64, P, P, P, P]),
             "cel_namespace_rows": (i32, [P, P, u32, u32, P, u64, u64, u64] + [P] * 12),
+            "cel_dev_tree_index_batch_size": (sz, [u32, u32]),
+            "cel_dev_tree_index_build_batch": (i32, [P, P, u32, u32, P, P, P, P, P, u32, P]),
+            "cel_dev_prove_squares_workspace_size": (sz, [u32]),
+            "cel_dev_prove_squares": (i32, [P, P, P, u32, u32, u32, P, P, P, P, P, P, P, P, P]),
+            "cel_dev_namespace_squares_workspace_size": (sz, [u32, u32]),
+            "cel_dev_namespace_plan_squares": (i32, [P, P, u32, u32, u32, P, P, u64, P, P, P, P, P, P, P, P, P, P]),
+            "cel_dev_namespace_prove_squares": (i32, [P, P, P, u32, u32, u64, P, P, P, P]),
+            "cel_prove_samples_squares": (i32, [P, P, u32, u32, u32, P, P, P, P, P, P, P]),
+            "cel_namespace_rows_squares": (i32, [P, P, u32, u32, u32, P, P, u64, u64, u64] + [P] * 12),
             "cel_nmt_verify_namespace_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, P, u32, P, P]),
             "cel_dev_nmt_verify_namespace_workspace_size": (sz, [u64, u64, u32]),
             "cel_dev_nmt_verify_namespace_batch": (i32, [P, u32, P, P, P, P, P, P, P, P, P, u32, P, P, P, P]),

@@ -910,6 +910,177 @@ class TreeIndex:
         return _square.units_from_records(recs, status, data, len(ranges))
 
 
+class TreeIndexBatch:
+    """Many squares resident on the device with their tree indexes, for a node that serves
+    samples and namespace queries over many heights at once. `squares`: ExtendedDataSquares or
+    (2k, 2k, 512) arrays of mixed widths; they are grouped by width as ExtendBlocks groups blocks,
+    one cel_dev_tree_index_build_batch per width, and a call's requests go to the device once per
+    width (cel_dev_prove_squares, cel_dev_namespace_plan_squares). row_roots[i], col_roots[i],
+    dah[i] and status[i] are square i's, in the caller's order. With order_check a square whose
+    shares are not in namespace order keeps its status (EORDER) and the rest are served; a
+    request that names such a square raises CelError."""
+
+    def __init__(self, squares, ctx=None, order_check=False):
+        import torch
+        cells = [np.ascontiguousarray(getattr(s, "cells", s), dtype=np.uint8) for s in squares]
+        self.ctx = ctx or next((s._ctx for s in squares if getattr(s, "_ctx", None)), None) or _lib.default_context()
+        c = self.ctx
+        self._torch = torch
+        self._dev = torch.device("cuda", c.device)
+        self._stream = torch.cuda.Stream(device=self._dev)
+        self.n = len(cells)
+        self.widths = []
+        self._where = []   # square i -> (its width, its place among the squares of that width)
+        self._groups = {}  # width -> dict(ids, d_eds, d_index, d_roots)
+        for i, x in enumerate(cells):
+            if x.ndim != 3 or x.shape[0] != x.shape[1] or x.shape[2] != _lib.SHARE_SIZE:
+                raise CelError(_lib.EINVAL, f"square {i}: need a (2k, 2k, {_lib.SHARE_SIZE}) square, got {x.shape}")
+            w = x.shape[0]
+            if w < 2 or c.lib.cel_dev_tree_index_batch_size(w // 2, 1) == 0 or w % 2:
+                raise CelError(_lib.ENOTPOW2, f"square {i}: square width is not a power of 2: got {w / 2:g}")
+            g = self._groups.setdefault(w, dict(ids=[]))
+            self._where.append((w, len(g["ids"])))
+            g["ids"].append(i)
+            self.widths.append(w)
+        self.row_roots, self.col_roots = [None] * self.n, [None] * self.n
+        self.dah, self.status = [None] * self.n, [0] * self.n
+        flags = _lib.FLAG_ORDER_CHECK if order_check else 0
+        with torch.cuda.stream(self._stream):
+            for w, g in self._groups.items():
+                m, k = len(g["ids"]), w // 2
+                g["d_eds"] = torch.as_tensor(np.stack([cells[i] for i in g["ids"]])).to(self._dev)
+                g["d_index"] = torch.empty((c.lib.cel_dev_tree_index_batch_size(k, m),), dtype=torch.uint8,
+                                           device=self._dev)
+                g["d_roots"] = torch.empty((2, m, w, NODE), dtype=torch.uint8, device=self._dev)
+                d_dah = torch.empty((m, 32), dtype=torch.uint8, device=self._dev)
+                status = np.full(m, -1, np.int32)
+                c.check(c.lib.cel_dev_tree_index_build_batch(
+                    c.handle, self._ptr(g["d_eds"]), m, k, self._ptr(g["d_index"]), self._ptr(g["d_roots"][0]),
+                    self._ptr(g["d_roots"][1]), self._ptr(d_dah), _p(status), flags, self._stream_ptr()))
+                self._stream.synchronize()
+                roots, dahs = g["d_roots"].cpu().numpy(), d_dah.cpu().numpy()
+                for j, i in enumerate(g["ids"]):
+                    self.row_roots[i] = [r.tobytes() for r in roots[0, j]]
+                    self.col_roots[i] = [r.tobytes() for r in roots[1, j]]
+                    self.dah[i] = dahs[j].tobytes()
+                    self.status[i] = int(status[j])
+
+    _ptr = staticmethod(TreeIndex._ptr)
+    _stream_ptr = TreeIndex._stream_ptr
+
+    def _by_width(self, squares, what):
+        """Request numbers per width, in request order; a square that is not there or not served raises."""
+        out = {}
+        for i, sq in enumerate(squares):
+            if not 0 <= sq < self.n:
+                raise CelError(_lib.EINVAL, f"{what} {i}: square {sq} of {self.n}")
+            if self.status[sq] != _lib.OK:
+                raise CelError(self.status[sq], f"{what} {i}: square {sq}: invalid push order: a namespace is smaller "
+                                                "than the previous one")
+            out.setdefault(self._where[sq][0], []).append(i)
+        return out
+
+    def prove_flat(self, squares, axes, index, starts, ends, shares=True):
+        """Proof i = ProveRange(starts[i], ends[i]) on row (axes[i] = 0) or column (1) index[i] of
+        square squares[i]: (leaves [total leaves][512] or None, nodes [total nodes][90], leaf_off,
+        node_off) in request order, the flat layout of cel_nmt_verify_batch. One
+        cel_dev_prove_squares per width among the requests."""
+        torch, c = self._torch, self.ctx
+        squares = [int(s) for s in squares]
+        axes, index = np.ascontiguousarray(axes, np.uint8), np.ascontiguousarray(index, np.uint32)
+        starts, ends = np.ascontiguousarray(starts, np.int32), np.ascontiguousarray(ends, np.int32)
+        n = len(squares)
+        if not (len(axes) == len(index) == len(starts) == len(ends) == n):
+            raise CelError(_lib.EINVAL, "squares, axes, index, starts and ends differ in number")
+        nl, nn = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        parts = {}
+        for w, ids in self._by_width(squares, "proof").items():
+            g, ids = self._groups[w], np.array(ids)
+            sq = np.array([self._where[squares[i]][1] for i in ids], np.uint32)
+            a, t, s, e = (np.ascontiguousarray(v[ids]) for v in (axes, index, starts, ends))
+            lo, no = prove_offsets(w // 2, s, e)
+            nl[ids], nn[ids] = np.diff(lo), np.diff(no)
+            tl, tn = int(lo[-1]), int(no[-1])
+            with torch.cuda.stream(self._stream):
+                d_leaves = torch.empty((tl, _lib.SHARE_SIZE), dtype=torch.uint8, device=self._dev) if shares else None
+                d_nodes = torch.empty((max(tn, 1), NODE), dtype=torch.uint8, device=self._dev)
+                d_work = torch.empty((c.lib.cel_dev_prove_squares_workspace_size(len(ids)),), dtype=torch.uint8,
+                                     device=self._dev)
+                c.check(c.lib.cel_dev_prove_squares(
+                    c.handle, self._ptr(g["d_eds"]), self._ptr(g["d_index"]), w // 2, len(g["ids"]), len(ids), _p(sq),
+                    _p(a), _p(t), _p(s), _p(e), self._ptr(d_leaves) if shares else None, self._ptr(d_nodes),
+                    self._ptr(d_work), self._stream_ptr()))
+                self._stream.synchronize()
+                parts[w] = (ids, d_leaves.cpu().numpy() if shares else None, d_nodes[:tn].cpu().numpy(), lo, no)
+        leaf_off = np.concatenate([[0], np.cumsum(nl)]).astype(np.uint64)
+        node_off = np.concatenate([[0], np.cumsum(nn)]).astype(np.uint64)
+        leaves = np.zeros((int(leaf_off[-1]), _lib.SHARE_SIZE), np.uint8) if shares else None
+        nodes = np.zeros((int(node_off[-1]), NODE), np.uint8)
+        for ids, pl, pn, lo, no in parts.values():  # each width's outputs to the requests' own places
+            for j, i in enumerate(ids):
+                nodes[int(node_off[i]):int(node_off[i + 1])] = pn[int(no[j]):int(no[j + 1])]
+                if shares:
+                    leaves[int(leaf_off[i]):int(leaf_off[i + 1])] = pl[int(lo[j]):int(lo[j + 1])]
+        return leaves, nodes, leaf_off, node_off
+
+    def prove_samples(self, samples):
+        """Samples (square, row, col, axis) -> (row, col, axis, share, nodes) each, what
+        TreeIndex.prove_samples gives for that square: RepairFromSamples' format."""
+        reqs = [(int(q), int(r), int(c), int(a)) for q, r, c, a in samples]
+        for i, (q, r, c, a) in enumerate(reqs):
+            w = self.widths[q] if 0 <= q < self.n else 0
+            if w and not (0 <= r < w and 0 <= c < w and 0 <= a <= 1):
+                raise CelError(_lib.EINVAL, f"sample {i}: cell ({r}, {c}) axis {a} outside the square of width {w}")
+        index = [c if a else r for _, r, c, a in reqs]
+        starts = [r if a else c for _, r, c, a in reqs]
+        leaves, nodes, _, node_off = self.prove_flat([q for q, _, _, _ in reqs], [a for _, _, _, a in reqs], index,
+                                                     starts, [s + 1 for s in starts])
+        return [(r, c, a, leaves[i].tobytes(), [nodes[j].tobytes() for j in range(int(node_off[i]), int(node_off[i + 1]))])
+                for i, (_, r, c, a) in enumerate(reqs)]
+
+    def namespace_rows(self, queries):
+        """Queries (square, namespace) -> per query what TreeIndex.namespace_rows gives for that
+        namespace on that square: a list of (row, NMTProof, shares), rows ascending. One
+        cel_dev_namespace_plan_squares and one cel_dev_namespace_prove_squares per width."""
+        torch, c = self._torch, self.ctx
+        qs = [(int(q), bytes(ns)) for q, ns in queries]
+        if any(len(ns) != NS for _, ns in qs):
+            raise CelError(_lib.EINVAL, f"a namespace is {NS} bytes")
+        out = [[] for _ in qs]
+        for w, ids in self._by_width([q for q, _ in qs], "query").items():
+            g, k, n = self._groups[w], w // 2, len(ids)
+            sq = np.array([self._where[qs[i][0]][1] for i in ids], np.uint32)
+            ns = np.frombuffer(b"".join(qs[i][1] for i in ids), np.uint8).copy()
+            cnt, cap = ctypes.c_uint64(0), n * w
+            with torch.cuda.stream(self._stream):
+                d_work = torch.empty((max(c.lib.cel_dev_namespace_squares_workspace_size(k, n), 16),), dtype=torch.uint8,
+                                     device=self._dev)
+                f = dict(query_idx=np.zeros(cap, np.uint32), rows=np.zeros(cap, np.uint32), starts=np.zeros(cap, np.int32),
+                         ends=np.zeros(cap, np.int32), kinds=np.zeros(cap, np.uint8), leaf_off=np.zeros(cap + 1, np.uint64),
+                         node_off=np.zeros(cap + 1, np.uint64))
+                c.check(c.lib.cel_dev_namespace_plan_squares(
+                    c.handle, self._ptr(g["d_index"]), k, len(g["ids"]), n, _p(sq), _p(ns), cap, _p(f["query_idx"]),
+                    _p(f["rows"]), _p(f["starts"]), _p(f["ends"]), _p(f["kinds"]), _p(f["leaf_off"]), _p(f["node_off"]),
+                    ctypes.byref(cnt), self._ptr(d_work), self._stream_ptr()))
+                m = cnt.value
+                tl, tn = int(f["leaf_off"][m]), int(f["node_off"][m])
+                d_leaves = torch.empty((max(tl, 1), _lib.SHARE_SIZE), dtype=torch.uint8, device=self._dev)
+                d_nodes = torch.empty((max(tn, 1), NODE), dtype=torch.uint8, device=self._dev)
+                c.check(c.lib.cel_dev_namespace_prove_squares(
+                    c.handle, self._ptr(g["d_eds"]), self._ptr(g["d_index"]), k, len(g["ids"]), m, self._ptr(d_leaves),
+                    self._ptr(d_nodes), self._ptr(d_work), self._stream_ptr()))
+                self._stream.synchronize()
+                leaves, nodes = d_leaves[:tl].cpu().numpy(), d_nodes[:tn].cpu().numpy()
+            for e in range(m):
+                nd = [nodes[j].tobytes() for j in range(int(f["node_off"][e]), int(f["node_off"][e + 1]))]
+                absent = int(f["kinds"][e]) == NS_ABSENCE
+                p = NMTProof(Start=int(f["starts"][e]), End=int(f["ends"][e]), Nodes=nd[:-1] if absent else nd,
+                             LeafHash=nd[-1] if absent else None)
+                shares = [leaves[j].tobytes() for j in range(int(f["leaf_off"][e]), int(f["leaf_off"][e + 1]))]
+                out[ids[int(f["query_idx"][e])]].append((int(f["rows"][e]), p, shares))
+        return out
+
+
 def NewShareInclusionProofsBatch(eds, requests, ctx=None):
     """NewShareInclusionProofFromEDS(eds, namespace, start, end) for every (namespace, start,
     end) of `requests`, from one tree index: each request splits into per-row ranges as

@@ -477,3 +477,99 @@ def RepairFromSamples(k, samples, row_roots, col_roots, ctx=None):
     sq._row_roots = rr.reshape(w, -1).copy()
     sq._col_roots = cr.reshape(w, -1).copy()
     return sq, ok
+
+
+def _squares_by_width(squares, picks, what):
+    """`squares` as (W, W, 512) arrays, and the numbers of the requests whose square (picks[i]) has
+    each width, in request order: {W: (the squares of that width that are asked for, their
+    stacked cells, request numbers)}."""
+    cells = [np.ascontiguousarray(getattr(s, "cells", s), dtype=np.uint8) for s in squares]
+    groups = {}
+    for i, q in enumerate(picks):
+        if not 0 <= q < len(cells):
+            raise CelError(_lib.EINVAL, f"{what} {i}: square {q} of {len(cells)}")
+        x = cells[q]
+        if x.ndim != 3 or x.shape[0] != x.shape[1] or x.shape[2] != _lib.SHARE_SIZE:
+            raise CelError(_lib.EINVAL, f"square {q}: need a (2k, 2k, {_lib.SHARE_SIZE}) square, got {x.shape}")
+        sqs, ids = groups.setdefault(x.shape[0], ([], []))
+        if q not in sqs:
+            sqs.append(q)
+        ids.append(i)
+    return {w: (sqs, np.stack([cells[q] for q in sqs]), ids) for w, (sqs, ids) in groups.items()}
+
+
+def SampleProofsBatch(squares, samples, ctx=None):
+    """ExtendedDataSquare.SampleProofs over many squares at once: samples = (square, row, col,
+    axis) each, `square` a position in `squares` (ExtendedDataSquares or (2k, 2k, 512) arrays,
+    mixed widths). The squares that are asked for go up grouped by width, one
+    cel_prove_samples_squares per width (upload, batch tree index, proofs, download). Returns
+    (square, row, col, axis, share, nodes) per sample, in the samples' order; the last five are
+    RepairFromSamples' format."""
+    ctx = ctx or next((s._ctx for s in squares if getattr(s, "_ctx", None)), None) or _lib.default_context()
+    reqs = [(int(q), int(r), int(c), int(a)) for q, r, c, a in samples]
+    out = [None] * len(reqs)
+    share, node = _lib.SHARE_SIZE, _lib.NMT_NODE_SIZE
+    for w, (sqs, cells, ids) in _squares_by_width(squares, [q for q, _, _, _ in reqs], "sample").items():
+        for i in ids:
+            _, r, c, a = reqs[i]
+            if not (0 <= r < w and 0 <= c < w and a in (Row, Col)):
+                raise CelError(_lib.EINVAL, f"sample {i}: cell ({r}, {c}) axis {a} outside the square of width {w}")
+        n, per = len(ids), w.bit_length() - 1
+        sq = np.array([sqs.index(reqs[i][0]) for i in ids], np.uint32)
+        rows = np.array([reqs[i][1] for i in ids], np.uint32)
+        cols = np.array([reqs[i][2] for i in ids], np.uint32)
+        axes = np.array([reqs[i][3] for i in ids], np.uint8)
+        shares, nodes = np.zeros((n, share), np.uint8), np.zeros((max(n * per, 1), node), np.uint8)
+        node_off = np.zeros(n + 1, np.uint64)
+        ctx.check(ctx.lib.cel_prove_samples_squares(ctx.handle, _p(cells), len(sqs), w // 2, n, _p(sq), _p(rows), _p(cols),
+                                                    _p(axes), _p(shares), _p(nodes), _p(node_off)))
+        for j, i in enumerate(ids):
+            out[i] = reqs[i] + (shares[j].tobytes(),
+                                [nodes[t].tobytes() for t in range(int(node_off[j]), int(node_off[j + 1]))])
+    return out
+
+
+def SharesByNamespaceBatch(squares, queries, ctx=None):
+    """ExtendedDataSquare.SharesByNamespace over many squares at once: queries = (square,
+    namespace) each. Returns, per query, what squares[square].SharesByNamespace(namespace)
+    returns: (row, NMTProof, shares) for each row whose root range holds the namespace. One
+    cel_namespace_rows_squares per width, called twice as SharesByNamespace calls the
+    single-square form twice: once for the counts, once for the entries. Each call uploads that
+    width's squares and builds their index, so a width costs two uploads and two index builds; a
+    caller that asks the same squares more than once keeps them resident with
+    proof.TreeIndexBatch, which uploads and indexes once and plans once per call. The parity
+    namespace raises CelError(EINVAL); a square whose shares are not in namespace order,
+    CelError(EORDER)."""
+    from .proof import NMTProof
+    ctx = ctx or next((s._ctx for s in squares if getattr(s, "_ctx", None)), None) or _lib.default_context()
+    qs = [(int(q), bytes(ns)) for q, ns in queries]
+    if any(len(ns) != _lib.NAMESPACE_SIZE for _, ns in qs):
+        raise CelError(_lib.EINVAL, f"a namespace is {_lib.NAMESPACE_SIZE} bytes")
+    out = [[] for _ in qs]
+    share, node = _lib.SHARE_SIZE, _lib.NMT_NODE_SIZE
+    for w, (sqs, cells, ids) in _squares_by_width(squares, [q for q, _ in qs], "query").items():
+        n = len(ids)
+        sq = np.array([sqs.index(qs[i][0]) for i in ids], np.uint32)
+        nsa = np.frombuffer(b"".join(qs[i][1] for i in ids), np.uint8).copy()
+        cnt, tl, tn = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        tail = (ctypes.byref(cnt), ctypes.byref(tl), ctypes.byref(tn))
+        ctx.check(ctx.lib.cel_namespace_rows_squares(ctx.handle, _p(cells), len(sqs), w // 2, n, _p(sq), _p(nsa), 0, 0, 0,
+                                                     *([None] * 9), *tail))
+        m = cnt.value
+        if m == 0:
+            continue
+        qi, rows = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        starts, ends, kinds = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+        leaf_off, node_off = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64)
+        leaves, nodes = np.zeros((max(tl.value, 1), share), np.uint8), np.zeros((max(tn.value, 1), node), np.uint8)
+        ctx.check(ctx.lib.cel_namespace_rows_squares(ctx.handle, _p(cells), len(sqs), w // 2, n, _p(sq), _p(nsa), m,
+                                                     tl.value, tn.value, _p(qi), _p(rows), _p(starts), _p(ends), _p(kinds),
+                                                     _p(leaf_off), _p(node_off), _p(leaves), _p(nodes), *tail))
+        for e in range(m):
+            nd = [nodes[j].tobytes() for j in range(int(node_off[e]), int(node_off[e + 1]))]
+            absent = int(kinds[e]) == _lib.NS_ABSENCE
+            out[ids[int(qi[e])]].append((int(rows[e]),
+                                         NMTProof(Start=int(starts[e]), End=int(ends[e]), Nodes=nd[:-1] if absent else nd,
+                                                  LeafHash=nd[-1] if absent else None),
+                                         [leaves[j].tobytes() for j in range(int(leaf_off[e]), int(leaf_off[e + 1]))]))
+    return out

@@ -87,6 +87,11 @@ void cel_ctx_destroy(cel_ctx* ctx) {
       (void)hipEventDestroy(ctx->plan_up.ev);
     }
     if (ctx->plan_up.buf) (void)hipHostFree(ctx->plan_up.buf);
+    if (ctx->ev_ix_status) {
+      (void)hipEventSynchronize(ctx->ev_ix_status);  // a caller stream may still read the status array
+      (void)hipEventDestroy(ctx->ev_ix_status);
+    }
+    if (ctx->ix_status) (void)hipFree(ctx->ix_status);
     free_tables(&ctx->tables);
     for (int i = 0; i < cel_ctx::kPipe; i++)
       if (ctx->sub[i]) (void)hipStreamDestroy(ctx->sub[i]);

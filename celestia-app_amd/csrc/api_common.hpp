@@ -175,6 +175,13 @@ cel_status dev_repair_locked(cel_ctx* ctx, void* d_eds, uint8_t* present, uint32
                              const uint8_t* col_roots, int32_t* bad_axis, int32_t* bad_index, uint8_t* byz_shares,
                              uint8_t* byz_present);
 
+// The batch tree index of n <= prove::kMaxSquares squares (api_prove.cpp), for a caller that holds
+// ctx->mu with the device current and the arguments checked; status (host, n, nullable) is copied
+// back on s. Shared with the namespace rows over many squares (api_namespace.cpp).
+cel_status index_batch_enqueue(cel_ctx* ctx, const uint8_t* d_eds, uint32_t n, uint32_t k, void* d_index,
+                               uint8_t* d_row_roots, uint8_t* d_col_roots, uint8_t* d_dah, int32_t* status,
+                               bool order_check, hipStream_t s);
+
 inline cel_status validate_square(cel_ctx* ctx, uint32_t k, uint32_t share_size) {
   if (share_size != kShare)
     return fail(ctx, CEL_ECHUNK, "share size must be appconsts.ShareSize (512) on the device path");

@@ -374,6 +374,14 @@ struct cel_ctx {
   cel::StagedUpload plan_up, square_up;
   hipEvent_t ev_sq_done = nullptr;
   bool sq_built = false;
+  // cel_dev_tree_index_build_batch: the squares' statuses as one device array (the index keeps
+  // each in its slice's tail, an index size apart), so that they go back in one copy. The copy
+  // reads it until ev_ix_status; the next build's stream waits for that event before its DAH
+  // kernel writes the array again, and a build that has to grow it waits on the host.
+  int32_t* ix_status = nullptr;
+  size_t ix_status_n = 0;
+  hipEvent_t ev_ix_status = nullptr;
+  bool ix_status_pending = false;
   // The last cel_block_extend_batch on this ctx: each block's message ("" where it is CEL_OK),
   // for cel_block_batch_error.
   std::vector<std::string> block_errors;

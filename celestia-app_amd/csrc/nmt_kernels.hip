@@ -27,7 +27,9 @@
 //
 // This file is the EDS commit, and the build of a square's tree index (launch_tree_index: the
 // single-square commit with every level kept, nmt_prove.hpp; the proofs from it are
-// nmt_prove.hip). The row-sharded mode is nmt_slab.hip; single trees, the
+// nmt_prove.hip), and the same for many squares in one launch per step (launch_tree_index_batch:
+// k_leaf_index, k_level_index, k_merkle_index, with their bounds argument, near the end of the
+// file). The row-sharded mode is nmt_slab.hip; single trees, the
 // repair's axes roots, exported trees and the byte-slice hash are nmt_trees.hip.
 #include <hip/hip_runtime.h>
 
@@ -693,6 +695,174 @@ hipError_t launch_tree_index(const uint8_t* eds, uint32_t k, void* d_index, uint
   }
   const Range r("dah");
   launch_merkle(level(x.L), leafd, 2 * x.W, 1, dah, bad, status, s, nullptr, nullptr, 0);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------- the batch tree index
+//
+// The tree index of n squares in one launch per step (nmt_prove.hpp: n single-square indexes
+// back to back). These are k_leaf, k_level and k_merkle with the square's stride on both sides
+// the index's size: square blockIdx.y reads and writes inside its own slice, every level at
+// its slice_level_off, the leaf digests, the push-order flag, the DAH of a caller that wants none
+// and the status in the slice's tail. They are kernels of their own, so the instantiations the
+// commit and the single-square index launch take no new parameter; the hashing (make_leaf_node,
+// hash_pair, put_root, rfc_*) is shared.
+//
+// Bounds. The host checks k (a power of two up to 512) and nsq (1 .. prove::kMaxSquares, the
+// grid's y or x extent) and that the index holds nsq * index_bytes(W) bytes, the cells
+// nsq * W * W * 512, the roots nsq * 2W * 90 and a caller's DAH nsq * 32. A lane's cell is below
+// W * W and its level-l node below 2W * (W >> l), so with record = index_level_rec(W, l) + node
+// every record is below index_records(W); the tail offsets are below index_bytes(W). All of
+// them are added to slice = blockIdx * index_bytes(W) in 64 bits.
+
+__global__ __launch_bounds__(256) void k_index_bad_init(uint8_t* __restrict__ index, uint64_t slice, uint64_t bad_off,
+                                                        uint32_t nsq) {
+  const uint32_t sq = blockIdx.x * 256u + threadIdx.x;
+  if (sq < nsq) *reinterpret_cast<int32_t*>(index + (uint64_t)sq * slice + bad_off) = INT_MAX;
+}
+
+// grid: x = block of 256 cells, y = square. The leaf records of square y into level 0 of its slice.
+template <bool ORDER, bool PF>
+__global__ __launch_bounds__(256) void k_leaf_index(const uint8_t* __restrict__ eds, uint32_t k,
+                                                    uint8_t* __restrict__ index, uint64_t slice, uint64_t bad_off) {
+  const uint32_t W = 2 * k;
+  const uint32_t cell = blockIdx.x * 256u + threadIdx.x;
+  if (cell >= W * W) return;
+  const uint32_t r = cell / W, c = cell % W;
+  uint8_t* base = index + (uint64_t)blockIdx.y * slice;
+  const uint32_t* sh =
+      reinterpret_cast<const uint32_t*>(eds + prove::eds_base(W, blockIdx.y) + (uint64_t)cell * kShare);
+  const bool q0 = (r < k) && (c < k);
+  {
+    uint32_t nd[kNodeWords];
+    make_leaf_node<PF>(sh, q0, nd);
+    store_node(reinterpret_cast<uint32_t*>(base) + (uint64_t)cell * kNodeWords, nd);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // as in k_leaf: the order check after the hash
+  if (ORDER && q0) {
+    int32_t* bad = reinterpret_cast<int32_t*>(base + bad_off);
+    if (c > 0 && ns_less(sh, sh - kShare / 4)) atomicMin(bad, (int32_t)r);
+    if (r > 0 && ns_less(sh, sh - (uint64_t)W * kShare / 4)) atomicMin(bad, (int32_t)(W + c));
+  }
+}
+
+// k_level inside a slice: the level at in_off (nin nodes per tree, or the leaf records) into the
+// level at out_off. At the root level (row_out != nullptr) also the packed roots, [nsq][W][90]
+// each, and the roots' leaf digests at leafd_off.
+template <bool FROM_LEAVES>
+__global__ __launch_bounds__(256) void k_level_index(uint8_t* __restrict__ index, uint64_t slice, uint64_t in_off,
+                                                     uint64_t out_off, uint32_t W, uint32_t nin, uint32_t trees,
+                                                     uint64_t leafd_off, uint8_t* __restrict__ row_out,
+                                                     uint8_t* __restrict__ col_out) {
+  const uint32_t nout = nin / 2;
+  const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= trees * nout) return;
+  const uint32_t t = idx / nout, j = idx % nout;
+  uint8_t* base = index + (uint64_t)blockIdx.y * slice;
+  uint64_t li, ri;
+  if (FROM_LEAVES) {
+    if (t < W) { li = (uint64_t)t * W + 2 * j; ri = li + 1; }
+    else { li = (uint64_t)(2 * j) * W + (t - W); ri = li + W; }
+  } else {
+    li = (uint64_t)t * nin + 2 * j;
+    ri = li + 1;
+  }
+  uint32_t o[kNodeWords];
+  hash_pair(reinterpret_cast<const uint32_t*>(base + in_off), li, ri, o);
+  store_node(reinterpret_cast<uint32_t*>(base + out_off) + (uint64_t)idx * kNodeWords, o);
+  if (row_out) {
+    const uint64_t roots = (uint64_t)blockIdx.y * W * kNode;
+    put_root(o, 0, t, W, reinterpret_cast<uint32_t*>(base + leafd_off), row_out + roots, col_out + roots);
+  }
+}
+
+// k_merkle for square blockIdx.x of a batch index: RFC-6962 over the n = 4k leaf digests of its
+// slice. The DAH to dah + 32 * square, or to the slice's tail; with want_status the status to
+// the slice's tail and to status[square].
+__global__ __launch_bounds__(1024) void k_merkle_index(uint8_t* __restrict__ index, uint64_t slice, uint64_t leafd_off,
+                                                       uint32_t n, uint8_t* __restrict__ dah, uint64_t dah_off,
+                                                       uint64_t bad_off, uint64_t status_off,
+                                                       int32_t* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t hs[];  // n * 8 words
+  uint8_t* base = index + (uint64_t)blockIdx.x * slice;
+  const uint32_t* leafd = reinterpret_cast<const uint32_t*>(base + leafd_off);
+  for (uint32_t i = threadIdx.x; i < n * 8; i += blockDim.x) hs[i] = leafd[i];
+  __syncthreads();
+  uint32_t cnt = n;  // a power of two, at least 4
+  while (cnt > 1) {
+    const uint32_t half = cnt / 2;
+    uint32_t st[8];
+    for (uint32_t b = 0; b < half; b += blockDim.x) {
+      const uint32_t i = b + threadIdx.x;
+      if (i < half) rfc_inner(hs + (2 * i) * 8, hs + (2 * i + 1) * 8, st);
+      __syncthreads();
+      if (i < half) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) hs[i * 8 + j] = st[j];
+      }
+      __syncthreads();
+    }
+    cnt = half;
+  }
+  if (threadIdx.x == 0) {
+    uint8_t* out = dah ? dah + (uint64_t)blockIdx.x * 32 : base + dah_off;
+    for (int j = 0; j < 8; j++) {
+      const uint32_t v = hs[j];
+      out[4 * j] = (uint8_t)(v >> 24);
+      out[4 * j + 1] = (uint8_t)(v >> 16);
+      out[4 * j + 2] = (uint8_t)(v >> 8);
+      out[4 * j + 3] = (uint8_t)v;
+    }
+    if (status) {
+      const int32_t st = *reinterpret_cast<const int32_t*>(base + bad_off) != INT_MAX ? CEL_EORDER : CEL_OK;
+      *reinterpret_cast<int32_t*>(base + status_off) = st;
+      status[blockIdx.x] = st;
+    }
+  }
+}
+
+hipError_t launch_tree_index_batch(const uint8_t* eds, uint32_t k, uint32_t nsq, void* d_index, uint8_t* row_roots,
+                                   uint8_t* col_roots, uint8_t* dah, int32_t* status, bool order_check,
+                                   hipStream_t s) {
+  if (!nsq) return hipSuccess;
+  if (nsq > prove::kMaxSquares) return hipErrorInvalidValue;
+  const prove::IndexLayout x = prove::index_layout(k);
+  const uint32_t W = x.W;
+  const uint64_t slice = prove::index_bytes(W);
+  uint8_t* index = static_cast<uint8_t*>(d_index);
+  {
+    const Range r("index_batch.leaf");
+    hipLaunchKernelGGL(k_index_bad_init, dim3((nsq + 255) / 256), dim3(256), 0, s, index, slice,
+                       prove::slice_bad_off(W), nsq);
+    dim3 gl((W * W + 255) / 256, nsq);
+    dispatch_order_pf(order_check, latency_bound((uint64_t)W * W * nsq), [&](auto order, auto pf) {
+      hipLaunchKernelGGL((k_leaf_index<decltype(order)::value, decltype(pf)::value>), gl, dim3(256), 0, s, eds, k, index,
+                         slice, prove::slice_bad_off(W));
+    });
+  }
+  {
+    const Range r("index_batch.levels");
+    const uint32_t trees = 2 * W;
+    for (uint32_t l = 1; l <= x.L; l++) {
+      const bool root = l == x.L;
+      const uint32_t nin = W >> (l - 1);
+      dim3 g((trees * (nin / 2) + 255) / 256, nsq);
+      const uint64_t in_off = prove::slice_level_off(W, l - 1), out_off = prove::slice_level_off(W, l);
+      uint8_t* ro = root ? row_roots : nullptr;
+      uint8_t* co = root ? col_roots : nullptr;
+      if (l == 1)
+        hipLaunchKernelGGL(k_level_index<true>, g, dim3(256), 0, s, index, slice, in_off, out_off, W, nin, trees,
+                           prove::slice_leafd_off(W), ro, co);
+      else
+        hipLaunchKernelGGL(k_level_index<false>, g, dim3(256), 0, s, index, slice, in_off, out_off, W, nin, trees,
+                           prove::slice_leafd_off(W), ro, co);
+    }
+  }
+  const Range r("index_batch.dah");
+  const uint32_t n = 2 * W;
+  hipLaunchKernelGGL(k_merkle_index, dim3(nsq), dim3(merkle_block(n)), (size_t)n * 32, s, index, slice,
+                     prove::slice_leafd_off(W), n, dah, prove::slice_dah_off(W), prove::slice_bad_off(W),
+                     prove::slice_status_off(W), status);
   return hipGetLastError();
 }
 

@@ -34,6 +34,18 @@
 // [node0, node0 + nnodes) and shares at [leaf0, leaf0 + (end - start)): the prefix sums of
 // exactly those counts, which the plan call has given the caller to size the outputs with. It
 // runs over no more entries than the plan holds (head->totals.entries), whatever the caller passes.
+//
+// Over a batch index (k_ns_find_squares, k_ns_compact_squares, k_ns_emit_squares; the sums and
+// the scan are the same kernels). A query is a (square, namespace) pair; the host checks every
+// square < n_squares <= prove::kMaxSquares before it uploads the table (api_namespace.cpp), and
+// the caller's index holds n_squares slices and its cells n_squares squares. k_ns_find_squares
+// reads what k_ns_find reads, inside the slice at prove::slice_base of the query's square;
+// pairs, sums and entries are indexed by query and row as before, so the workspace argument is
+// unchanged and the order stays (query, row), fixed by pair number. k_ns_compact_squares reads
+// row ns_idx < n of the query table. k_ns_emit_squares takes the square from the entry, skips
+// an entry whose square is not below the n_squares it was launched for, and otherwise reads
+// what k_ns_emit reads inside that square's cells and slice; both bases are 64-bit. A plan's
+// head says which sort it is, and each emit kernel does nothing on the other sort.
 #include <hip/hip_runtime.h>
 
 #include "cel_internal.hpp"
@@ -67,23 +79,13 @@ __device__ __forceinline__ int ns_cmp(const uint32_t (&a)[8], const uint32_t (&b
   return res;
 }
 
-__global__ __launch_bounds__(256) void k_ns_find(const uint32_t* __restrict__ index, uint32_t W, uint32_t L,
-                                                 const uint32_t* __restrict__ ns, uint32_t n,
-                                                 Pair* __restrict__ pairs) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t groups = (W + 63u) / 64u;  // of 64 rows, per namespace
-  // n * groups <= n * W < 2^32
-  const uint64_t g64 = (uint64_t)blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6);
-  if (g64 >= (uint64_t)n * groups) return;
-  const uint32_t g = __builtin_amdgcn_readfirstlane((uint32_t)g64);
-  const uint32_t qi = g / groups, row0 = (g - qi * groups) * 64u;
+// One wave of the find: query qi (its 8 raw words in `raw`) against rows row0 .. row0 + 63 of the
+// square whose index is at `index`.
+__device__ __forceinline__ void ns_find_rows(const uint32_t* __restrict__ index, uint32_t W, uint32_t L,
+                                             const uint32_t (&raw)[8], uint32_t qi, uint32_t row0,
+                                             Pair* __restrict__ pairs, uint32_t lane) {
   uint32_t nid[8];
-  {
-    uint32_t raw[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) raw[i] = ns[(uint64_t)qi * 8 + i];
-    min_be(raw, nid);
-  }
+  min_be(raw, nid);
   // lane r: does the root of row row0 + r hold the namespace? An empty pair if not.
   const uint32_t myrow = row0 + lane;
   bool inside = false;
@@ -124,6 +126,41 @@ __global__ __launch_bounds__(256) void k_ns_find(const uint32_t* __restrict__ in
     }
     if (lane == 0) pairs[(uint64_t)qi * W + row] = nsq::classify(true, lt, le, W);
   }
+}
+
+__global__ __launch_bounds__(256) void k_ns_find(const uint32_t* __restrict__ index, uint32_t W, uint32_t L,
+                                                 const uint32_t* __restrict__ ns, uint32_t n,
+                                                 Pair* __restrict__ pairs) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t groups = (W + 63u) / 64u;  // of 64 rows, per namespace
+  // n * groups <= n * W < 2^32
+  const uint64_t g64 = (uint64_t)blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6);
+  if (g64 >= (uint64_t)n * groups) return;
+  const uint32_t g = __builtin_amdgcn_readfirstlane((uint32_t)g64);
+  const uint32_t qi = g / groups, row0 = (g - qi * groups) * 64u;
+  uint32_t raw[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) raw[i] = ns[(uint64_t)qi * 8 + i];
+  ns_find_rows(index, W, L, raw, qi, row0, pairs, lane);
+}
+
+// k_ns_find over a batch index: query qi is a (square, namespace) pair, the square in the three
+// bytes that pad its namespace to 32 (nsq::query_square), and the wave reads the root level and
+// the leaves of that square's slice.
+__global__ __launch_bounds__(256) void k_ns_find_squares(const uint8_t* __restrict__ index, uint32_t W, uint32_t L,
+                                                         const uint32_t* __restrict__ ns, uint32_t n,
+                                                         Pair* __restrict__ pairs) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t groups = (W + 63u) / 64u;
+  const uint64_t g64 = (uint64_t)blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6);
+  if (g64 >= (uint64_t)n * groups) return;
+  const uint32_t g = __builtin_amdgcn_readfirstlane((uint32_t)g64);
+  const uint32_t qi = g / groups, row0 = (g - qi * groups) * 64u;
+  uint32_t raw[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) raw[i] = ns[(uint64_t)qi * 8 + i];
+  const uint32_t sq = nsq::query_square(raw[7]);
+  ns_find_rows(reinterpret_cast<const uint32_t*>(index + prove::slice_base(W, sq)), W, L, raw, qi, row0, pairs, lane);
 }
 
 // The counters of pair p; zero beyond the table.
@@ -218,10 +255,13 @@ __global__ __launch_bounds__(256) void k_ns_scan(Sums* __restrict__ block_sums, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_ns_compact(const Pair* __restrict__ pairs, uint64_t npairs, uint32_t W,
-                                                    uint32_t L, const Sums* __restrict__ block_sums,
-                                                    Request* __restrict__ req) {
-  __shared__ uint32_t sh[kWavesPerGroup * 3];
+// A block of the compaction. SQUARES: the plan is over a batch index, and the entry takes its
+// query's square above its kind (nsq::entry_kind / nsq::entry_square) from the query table ns.
+template <bool SQUARES>
+__device__ __forceinline__ void ns_compact_block(const Pair* __restrict__ pairs, uint64_t npairs, uint32_t W,
+                                                 uint32_t L, const Sums* __restrict__ block_sums,
+                                                 const uint32_t* __restrict__ ns, Request* __restrict__ req,
+                                                 uint32_t* sh) {
   const uint64_t p = (uint64_t)blockIdx.x * nsq::kScanBlock + threadIdx.x;
   Pair pr;
   uint32_t e, nn, nl, tot[3];
@@ -236,11 +276,51 @@ __global__ __launch_bounds__(256) void k_ns_compact(const Pair* __restrict__ pai
   r.row = (uint32_t)(p % W);
   r.start = (int32_t)pr.start;
   r.end = (int32_t)pr.end;
-  r.kind = pr.kind;
+  r.kind = SQUARES ? nsq::entry_pack(pr.kind, nsq::query_square(ns[(uint64_t)r.ns_idx * 8 + 7])) : pr.kind;
   r.nnodes = nn;
   r.node0 = base.nodes + (in - nn);
   r.leaf0 = base.leaves + (il - nl);
   req[base.entries + (ie - 1)] = r;
+}
+
+__global__ __launch_bounds__(256) void k_ns_compact(const Pair* __restrict__ pairs, uint64_t npairs, uint32_t W,
+                                                    uint32_t L, const Sums* __restrict__ block_sums,
+                                                    Request* __restrict__ req) {
+  __shared__ uint32_t sh[kWavesPerGroup * 3];
+  ns_compact_block<false>(pairs, npairs, W, L, block_sums, nullptr, req, sh);
+}
+
+__global__ __launch_bounds__(256) void k_ns_compact_squares(const Pair* __restrict__ pairs, uint64_t npairs,
+                                                            uint32_t W, uint32_t L,
+                                                            const Sums* __restrict__ block_sums,
+                                                            const uint32_t* __restrict__ ns,
+                                                            Request* __restrict__ req) {
+  __shared__ uint32_t sh[kWavesPerGroup * 3];
+  ns_compact_block<true>(pairs, npairs, W, L, block_sums, ns, req, sh);
+}
+
+// Entry q, of kind `kind`, of the square whose cells are at eds and whose index is at index.
+__device__ __forceinline__ void ns_emit_entry(const uint8_t* __restrict__ eds, const uint16_t* __restrict__ index,
+                                              uint32_t W, uint32_t L, const Request& q, uint32_t kind,
+                                              uint8_t* __restrict__ leaves, uint8_t* __restrict__ nodes,
+                                              uint32_t lane) {
+  const uint32_t s = (uint32_t)q.start, e1 = (uint32_t)q.end - 1u;
+  const uint32_t nn = q.nnodes;
+  const uint32_t np = nn - (kind == nsq::kAbsence ? 1u : 0u);  // ProveRange's nodes
+  uint32_t rec = 0;
+  if (lane < np) {
+    const prove::NodeAt a = prove::node_at(L, s, e1, lane);
+    rec = (uint32_t)prove::index_record(W, 0, q.row, a.level, a.pos);
+  } else if (lane < nn) {
+    rec = (uint32_t)prove::index_record(W, 0, q.row, 0, s);  // the leaf hash
+  }
+  copy_proof_nodes(rec, nn, index, reinterpret_cast<uint16_t*>(nodes + q.node0 * kNode), lane);
+  if (!leaves || kind != nsq::kInclusion) return;
+  const uint4* cells = reinterpret_cast<const uint4*>(eds);
+  uint4* lo = reinterpret_cast<uint4*>(leaves + q.leaf0 * kShare);
+  const uint32_t vecs = (uint32_t)(q.end - q.start) * kShareVecs;
+  const uint64_t cell0 = (uint64_t)q.row * W + s;
+  for (uint32_t t = lane; t < vecs; t += 64) lo[t] = cells[cell0 * kShareVecs + t];
 }
 
 __global__ __launch_bounds__(256) void k_ns_emit(const uint8_t* __restrict__ eds, const uint16_t* __restrict__ index,
@@ -251,23 +331,26 @@ __global__ __launch_bounds__(256) void k_ns_emit(const uint8_t* __restrict__ eds
   const uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6));
   if (i >= n_entries || i >= head->totals.entries || head->W != W) return;
   const Request q = reinterpret_cast<const Request*>(reinterpret_cast<const uint8_t*>(head) + nsq::kReqOff)[i];
-  const uint32_t s = (uint32_t)q.start, e1 = (uint32_t)q.end - 1u;
-  const uint32_t nn = q.nnodes;
-  const uint32_t np = nn - (q.kind == nsq::kAbsence ? 1u : 0u);  // ProveRange's nodes
-  uint32_t rec = 0;
-  if (lane < np) {
-    const prove::NodeAt a = prove::node_at(L, s, e1, lane);
-    rec = (uint32_t)prove::index_record(W, 0, q.row, a.level, a.pos);
-  } else if (lane < nn) {
-    rec = (uint32_t)prove::index_record(W, 0, q.row, 0, s);  // the leaf hash
-  }
-  copy_proof_nodes(rec, nn, index, reinterpret_cast<uint16_t*>(nodes + q.node0 * kNode), lane);
-  if (!leaves || q.kind != nsq::kInclusion) return;
-  const uint4* cells = reinterpret_cast<const uint4*>(eds);
-  uint4* lo = reinterpret_cast<uint4*>(leaves + q.leaf0 * kShare);
-  const uint32_t vecs = (uint32_t)(q.end - q.start) * kShareVecs;
-  const uint64_t cell0 = (uint64_t)q.row * W + s;
-  for (uint32_t t = lane; t < vecs; t += 64) lo[t] = cells[cell0 * kShareVecs + t];
+  ns_emit_entry(eds, index, W, L, q, q.kind, leaves, nodes, lane);
+}
+
+// k_ns_emit over a batch index, on a plan made over one (the head's width carries
+// nsq::kSquaresPlan; on any other plan the kernel does nothing): the entry names its square above
+// its kind, and the wave forms the two bases once. An entry whose square is not below n_squares,
+// which no plan made for these n_squares holds, is skipped.
+__global__ __launch_bounds__(256) void k_ns_emit_squares(const uint8_t* __restrict__ eds,
+                                                         const uint8_t* __restrict__ index, uint32_t W, uint32_t L,
+                                                         uint32_t n_squares, const nsq::Head* __restrict__ head,
+                                                         uint32_t n_entries, uint8_t* __restrict__ leaves,
+                                                         uint8_t* __restrict__ nodes) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerGroup + (threadIdx.x >> 6));
+  if (i >= n_entries || i >= head->totals.entries || head->W != (W | nsq::kSquaresPlan)) return;
+  const Request q = reinterpret_cast<const Request*>(reinterpret_cast<const uint8_t*>(head) + nsq::kReqOff)[i];
+  const uint32_t sq = nsq::entry_square(q.kind);
+  if (sq >= n_squares) return;
+  ns_emit_entry(eds + prove::eds_base(W, sq), reinterpret_cast<const uint16_t*>(index + prove::slice_base(W, sq)), W,
+                L, q, nsq::entry_kind(q.kind), leaves, nodes, lane);
 }
 
 }  // namespace
@@ -288,6 +371,33 @@ hipError_t launch_ns_plan(const void* d_index, uint32_t k, uint32_t n, const nsq
     hipLaunchKernelGGL(k_ns_compact, dim3((uint32_t)w.blocks), dim3(256), 0, s, w.pairs, w.npairs, x.W, x.L,
                        w.block_sums, w.req);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_ns_plan_squares(const void* d_index, uint32_t k, uint32_t n, const nsq::Work& w, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const prove::IndexLayout x = prove::index_layout(k);
+  const Range r("nmt_namespace_plan_squares");
+  const uint64_t waves = (uint64_t)n * ((x.W + 63) / 64);
+  hipLaunchKernelGGL(k_ns_find_squares, dim3((uint32_t)((waves + kWavesPerGroup - 1) / kWavesPerGroup)),
+                     dim3(64 * kWavesPerGroup), 0, s, static_cast<const uint8_t*>(d_index), x.W, x.L, w.ns, n, w.pairs);
+  hipLaunchKernelGGL(k_ns_sums, dim3((uint32_t)w.blocks), dim3(256), 0, s, w.pairs, w.npairs, x.L, w.block_sums);
+  // the head's width marks the plan as one over a batch index
+  hipLaunchKernelGGL(k_ns_scan, dim3(1), dim3(256), 0, s, w.block_sums, w.blocks, x.W | nsq::kSquaresPlan, w.head);
+  hipLaunchKernelGGL(k_ns_compact_squares, dim3((uint32_t)w.blocks), dim3(256), 0, s, w.pairs, w.npairs, x.W, x.L,
+                     w.block_sums, w.ns, w.req);
+  return hipGetLastError();
+}
+
+hipError_t launch_ns_emit_squares(const uint8_t* eds, const void* d_index, uint32_t k, uint32_t n_squares,
+                                  const void* d_work, uint32_t n_entries, uint8_t* d_leaves, uint8_t* d_nodes,
+                                  hipStream_t s) {
+  if (!n_entries) return hipSuccess;
+  const prove::IndexLayout x = prove::index_layout(k);
+  const Range r("nmt_namespace_emit_squares");
+  hipLaunchKernelGGL(k_ns_emit_squares, dim3((n_entries + kWavesPerGroup - 1) / kWavesPerGroup),
+                     dim3(64 * kWavesPerGroup), 0, s, eds, static_cast<const uint8_t*>(d_index), x.W, x.L, n_squares,
+                     static_cast<const nsq::Head*>(d_work), n_entries, d_leaves, d_nodes);
   return hipGetLastError();
 }
 

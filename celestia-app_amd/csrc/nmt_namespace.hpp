@@ -58,6 +58,29 @@ struct Request {
 };
 static_assert(sizeof(Request) == 40, "Request layout");
 
+// A plan over a batch index (nmt_prove.hpp: n_squares indexes back to back). Query i is a
+// (square, namespace) pair. Its row of the query table is the namespace's 29 bytes and the
+// square in the three bytes that pad it to 32, little-endian: the find kernel's compare words
+// drop those bytes, so the namespace compares as in a single-square plan. An entry of such a
+// plan carries its query's square above its kind, so the emit kernel needs nothing but the entry
+// to find the cells and the index slice; the plan call hands the caller the kind alone. The
+// head's W of such a plan has kSquaresPlan set: each emit kernel does nothing on a plan of the
+// other sort.
+constexpr uint32_t kSquaresPlan = 0x80000000u;
+constexpr uint32_t kMaxPlanSquares = 1u << 24;  // what three bytes hold; the calls take prove::kMaxSquares
+// Word 7 of a query's row of the table -> its square.
+CEL_PROVE_HD inline uint32_t query_square(uint32_t word7) { return word7 >> 8; }
+CEL_PROVE_HD inline uint32_t entry_pack(uint32_t kind, uint32_t square) { return kind | (square << 8); }
+CEL_PROVE_HD inline uint32_t entry_kind(uint32_t packed) { return packed & 0xFFu; }
+CEL_PROVE_HD inline uint32_t entry_square(uint32_t packed) { return packed >> 8; }
+// Row i of the query table from a namespace and a square < kMaxPlanSquares.
+inline void query_row(uint8_t* row, const uint8_t* ns29, uint32_t square) {
+  for (uint32_t j = 0; j < 29; j++) row[j] = ns29[j];
+  row[29] = (uint8_t)square;
+  row[30] = (uint8_t)(square >> 8);
+  row[31] = (uint8_t)(square >> 16);
+}
+
 // Running sums of the three counters a scan carries.
 struct Sums {
   uint64_t entries, nodes, leaves;
@@ -164,6 +187,13 @@ hipError_t launch_ns_plan(const void* d_index, uint32_t k, uint32_t n, const nsq
 // aligned.
 hipError_t launch_ns_emit(const uint8_t* eds, const void* d_index, uint32_t k, const void* d_work, uint32_t n_entries,
                           uint8_t* d_leaves, uint8_t* d_nodes, hipStream_t s);
+// The two over a batch index: w.ns holds the (square, namespace) query table (nsq::query_row),
+// every square below the number of squares the index holds; the emit runs over the entries whose
+// square is below n_squares.
+hipError_t launch_ns_plan_squares(const void* d_index, uint32_t k, uint32_t n, const nsq::Work& w, hipStream_t s);
+hipError_t launch_ns_emit_squares(const uint8_t* eds, const void* d_index, uint32_t k, uint32_t n_squares,
+                                  const void* d_work, uint32_t n_entries, uint8_t* d_leaves, uint8_t* d_nodes,
+                                  hipStream_t s);
 
 }  // namespace cel
 #endif

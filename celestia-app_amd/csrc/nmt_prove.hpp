@@ -2,7 +2,8 @@
 // the closed form of nmt ProveRange's node selection, and the per-proof table the kernel
 // reads. Everything above the device part (the node copy k_prove and k_ns_emit share, the
 // launcher declarations) is plain C++ with no HIP in it: tools/prove_select_check.cpp includes
-// this header alone and walks it on the host.
+// this header alone and walks it on the host, and tools/index_batch_check.cpp the arithmetic of
+// the batch index (many squares' indexes back to back).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -67,6 +68,39 @@ inline IndexLayout index_layout(uint32_t k) {
   return x;
 }
 
+// ------------------------------------------------------------------ batch index
+//
+// The indexes of n squares of one width, back to back: square sq's is a whole single-square
+// index (records and tail) at byte slice_base(W, sq), over the cells at eds_base(W, sq) of the n
+// squares' cells. Record numbers inside a slice stay 32-bit; the two bases are 64-bit byte
+// offsets (256 squares at k = 128 are 4.8 GB of index). The kernels of the batch build
+// (nmt_kernels.hip), k_prove_squares and the k_ns_*_squares kernels address through these, and
+// tools/index_batch_check.cpp walks them against index_record and index_layout.
+
+// Records of one index, all levels: index_level_rec(W, L + 1).
+CEL_PROVE_HD inline uint64_t index_records(uint32_t W) { return (uint64_t)W * W + (uint64_t)2 * W * (W - 1); }
+constexpr uint32_t kIndexTailFixed = 48;  // DAH, push-order flag, status, padding to 16
+// index_layout(k).bytes in closed form: a multiple of 16.
+CEL_PROVE_HD inline uint64_t index_bytes(uint32_t W) {
+  return index_records(W) * kRecordBytes + (uint64_t)2 * W * 32 + kIndexTailFixed;
+}
+CEL_PROVE_HD inline uint64_t slice_base(uint32_t W, uint32_t sq) { return (uint64_t)sq * index_bytes(W); }
+CEL_PROVE_HD inline uint64_t eds_base(uint32_t W, uint32_t sq) { return (uint64_t)sq * W * W * 512u; }
+// Byte offset of level l inside a slice: index_layout's level_off[l].
+CEL_PROVE_HD inline uint64_t slice_level_off(uint32_t W, uint32_t l) { return index_level_rec(W, l) * kRecordBytes; }
+// The tail inside a slice: leaf digests [2W][32], DAH, push-order flag, status.
+CEL_PROVE_HD inline uint64_t slice_leafd_off(uint32_t W) { return index_records(W) * kRecordBytes; }
+CEL_PROVE_HD inline uint64_t slice_dah_off(uint32_t W) { return slice_leafd_off(W) + (uint64_t)2 * W * 32; }
+CEL_PROVE_HD inline uint64_t slice_bad_off(uint32_t W) { return slice_dah_off(W) + 32; }
+CEL_PROVE_HD inline uint64_t slice_status_off(uint32_t W) { return slice_bad_off(W) + 4; }
+// Cell of leaf p of tree `index` along `axis`, inside its square: below W * W.
+CEL_PROVE_HD inline uint64_t request_cell(uint32_t W, uint32_t axis, uint32_t index, uint32_t p) {
+  return axis ? (uint64_t)p * W + index : (uint64_t)index * W + p;
+}
+// One launch takes the square in a grid dimension of 16 bits: a call over more squares is
+// rejected (CEL_EINVAL), not split.
+constexpr uint32_t kMaxSquares = 65535;
+
 // ------------------------------------------------- ProveRange's nodes, closed form
 //
 // nmt ProveRange(start, end) over 2^L leaves lists, left to right, the roots of the maximal
@@ -112,6 +146,14 @@ struct Request {
 };
 static_assert(sizeof(Request) == 32, "Request layout");
 
+// One proof of a batch over many squares (k_prove_squares): the request and the square it
+// names, whose cells and index slice lie at eds_base / slice_base.
+struct SquareRequest {
+  Request r;
+  uint32_t square, pad;
+};
+static_assert(sizeof(SquareRequest) == 40, "SquareRequest layout");
+
 }  // namespace prove
 }  // namespace cel
 
@@ -151,6 +193,17 @@ hipError_t launch_tree_index(const uint8_t* eds, uint32_t k, void* d_index, uint
 // nullable (then eds is not read); both 16-byte aligned. d_nodes 2-byte aligned.
 hipError_t launch_prove(const uint8_t* eds, const void* d_index, uint32_t k, const prove::Request* d_req, uint32_t n,
                         uint8_t* d_leaves, uint8_t* d_nodes, hipStream_t s);
+
+// The batch index of the nsq <= prove::kMaxSquares squares at eds (nmt_kernels.hip): per square
+// what launch_tree_index gives, square sq's index at prove::slice_base, its roots at
+// row_roots / col_roots + sq * 2k * 90, its DAH at dah + 32 * sq (dah nullable: each slice's
+// tail). status: device, [nsq], nullable; each slice's tail gets its own as well then.
+hipError_t launch_tree_index_batch(const uint8_t* eds, uint32_t k, uint32_t nsq, void* d_index, uint8_t* row_roots,
+                                   uint8_t* col_roots, uint8_t* dah, int32_t* status, bool order_check,
+                                   hipStream_t s);
+// n proofs over the squares of a batch index (nmt_prove.hip): request i names its square.
+hipError_t launch_prove_squares(const uint8_t* eds, const void* d_index, uint32_t k, const prove::SquareRequest* d_req,
+                                uint32_t n, uint8_t* d_leaves, uint8_t* d_nodes, hipStream_t s);
 
 }  // namespace cel
 #endif

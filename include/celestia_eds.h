@@ -659,6 +659,84 @@ cel_status cel_namespace_rows(cel_ctx* ctx, const uint8_t* eds, uint32_t k, uint
                               int32_t* ends, uint8_t* kinds, uint64_t* leaf_off, uint64_t* node_off,
                               uint8_t* leaves_out, uint8_t* nodes_out, uint64_t* n_entries,
                               uint64_t* total_leaves, uint64_t* total_nodes);
+/* ------------------------------------------------- many resident squares at once
+ * The index, the proofs and the namespace queries above over n squares of one width k that lie
+ * back to back at d_eds (n * 2k*2k*512 bytes), as cel_dev_extend_batch, cel_dev_repair_batch and
+ * a width group of cel_block_extend_batch leave them: one launch per step for all squares, one
+ * request table, one plan.
+ *
+ * The batch index is n single-square indexes back to back: square i's starts at d_index + i *
+ * cel_dev_tree_index_size(k) (a multiple of 16) and is byte for byte what
+ * cel_dev_tree_index_build gives for square i, so every single-square call (cel_dev_prove_batch,
+ * cel_dev_namespace_plan, cel_dev_blobs_*, cel_dev_txs_*) works on (d_eds + i * 2k*2k*512, d_index
+ * + i * size). cel_dev_tree_index_batch_size is n times cel_dev_tree_index_size(k): 0 where that
+ * is 0 (a k that is not a power of two or is above 2048), for n = 0, for n above 65535 and on
+ * overflow. As with the single pair, the size is given for more widths than the build takes: the
+ * calls below take k up to 512, the device path's limit.
+ * One call takes at most 65535 squares (a launch's grid holds the square in 16 bits): more is
+ * CEL_EINVAL in every call of this section, not split.
+ *
+ * cel_dev_tree_index_build_batch: per square exactly cel_dev_tree_index_build. d_row_roots /
+ * d_col_roots: [n][2k][90] each, d_dah: n*32 (nullable: each DAH goes to its slice's tail),
+ * status: host, n values (nullable), 0 or CEL_EORDER per square under CEL_FLAG_ORDER_CHECK; a
+ * square that fails the check does not touch the others. Asynchronous; status is copied back on
+ * the stream, in one copy, through one device array that the ctx keeps: a build that asks for
+ * status waits on the device for the status copy of the ctx's previous such build, so two of
+ * them on different streams of one ctx do not overlap, and the first build that needs a larger
+ * array waits for that copy on the host. A build with status = NULL has no such order. CEL_EINVAL: nil argument, misalignment, a bad k, too many squares. n = 0: CEL_OK.
+ *
+ * cel_dev_prove_squares: proof i = ProveRange(starts[i], ends[i]) on row or column index[i] of
+ * square squares[i] < n_squares. Outputs at cel_prove_offsets' prefix sums (they depend on the
+ * ranges only), so a batch whose requests all name square s is byte for byte cel_dev_prove_batch
+ * on slice s. Alignment, nullable d_leaves and CEL_EINVAL as there, and squares[i] >= n_squares
+ * (the request is named, nothing is enqueued). d_work: cel_dev_prove_squares_workspace_size(n).
+ *
+ * cel_dev_namespace_plan_squares / cel_dev_namespace_prove_squares: query i is the pair
+ * (squares[i], namespaces + 29*i); the entries come in (query, row) order and query_idx[e] names
+ * entry e's query. Everything else as cel_dev_namespace_plan / cel_dev_namespace_prove: count
+ * only with cap = 0, a cap below the count, the parity namespace, n * 2k < 2^32, the plan kept in
+ * d_work (cel_dev_namespace_squares_workspace_size(k, n) bytes) for the prove call, which takes
+ * the n_squares the plan was made for. A plan of one sort is nothing to the prove call of the
+ * other sort. CEL_EINVAL also for squares[i] >= n_squares. n = 0 or n_squares = 0 with nothing
+ * to do is CEL_OK.
+ *
+ * cel_prove_samples_squares / cel_namespace_rows_squares: the squares in host memory (eds:
+ * n_squares * 2k*2k*512): upload, batch index, proofs, download; synchronous; cel_prove_samples'
+ * and cel_namespace_rows' arguments with n_squares and squares[]. An unordered square is
+ * CEL_EORDER for the namespace rows, with the square named. */
+size_t cel_dev_tree_index_batch_size(uint32_t k, uint32_t n);
+cel_status cel_dev_tree_index_build_batch(cel_ctx* ctx, const void* d_eds, uint32_t n, uint32_t k,
+                                          void* d_index, void* d_row_roots, void* d_col_roots,
+                                          void* d_dah, int32_t* status, uint32_t flags, void* stream);
+size_t cel_dev_prove_squares_workspace_size(uint32_t n);
+cel_status cel_dev_prove_squares(cel_ctx* ctx, const void* d_eds, const void* d_index, uint32_t k,
+                                 uint32_t n_squares, uint32_t n, const uint32_t* squares,
+                                 const uint8_t* axes, const uint32_t* index, const int32_t* starts,
+                                 const int32_t* ends, void* d_leaves, void* d_nodes, void* d_work,
+                                 void* stream);
+size_t cel_dev_namespace_squares_workspace_size(uint32_t k, uint32_t n);
+cel_status cel_dev_namespace_plan_squares(cel_ctx* ctx, const void* d_index, uint32_t k,
+                                          uint32_t n_squares, uint32_t n, const uint32_t* squares,
+                                          const uint8_t* namespaces, uint64_t cap, uint32_t* query_idx,
+                                          uint32_t* rows, int32_t* starts, int32_t* ends,
+                                          uint8_t* kinds, uint64_t* leaf_off, uint64_t* node_off,
+                                          uint64_t* n_entries, void* d_work, void* stream);
+cel_status cel_dev_namespace_prove_squares(cel_ctx* ctx, const void* d_eds, const void* d_index,
+                                           uint32_t k, uint32_t n_squares, uint64_t n_entries,
+                                           void* d_leaves, void* d_nodes, void* d_work, void* stream);
+cel_status cel_prove_samples_squares(cel_ctx* ctx, const uint8_t* eds, uint32_t n_squares, uint32_t k,
+                                     uint32_t n, const uint32_t* squares, const uint32_t* rows,
+                                     const uint32_t* cols, const uint8_t* axes, uint8_t* shares_out,
+                                     uint8_t* nodes_out, uint64_t* node_off_out);
+cel_status cel_namespace_rows_squares(cel_ctx* ctx, const uint8_t* eds, uint32_t n_squares, uint32_t k,
+                                      uint32_t n, const uint32_t* squares, const uint8_t* namespaces,
+                                      uint64_t cap, uint64_t leaf_cap, uint64_t node_cap,
+                                      uint32_t* query_idx, uint32_t* rows, int32_t* starts,
+                                      int32_t* ends, uint8_t* kinds, uint64_t* leaf_off,
+                                      uint64_t* node_off, uint8_t* leaves_out, uint8_t* nodes_out,
+                                      uint64_t* n_entries, uint64_t* total_leaves,
+                                      uint64_t* total_nodes);
+
 /* nmt Proof.VerifyNamespace for n proofs: the arguments of cel_nmt_verify_batch and kinds[i]
  * (CEL_NS_INCLUSION / CEL_NS_ABSENCE; above 1: verdict 0). The leaves are whole 512-byte shares.
  * Inclusion: as cel_nmt_verify_batch, and every share starts with the namespace. Absence:
